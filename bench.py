@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- BA iterations/sec of the hand-written HIP bundle adjustment on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                         (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 A "step" is ONE full `BundleAdjustor::solve` of one synthetic sliding window (Ceres-1.14 Dogleg semantics, at most
 `solver.iteration_limit` = 10 trust-region iterations, config/euroc.yaml:66) with the window already resident in HBM
@@ -13,10 +14,20 @@ the gauge/marginalization prior).  `--workload vision` gives the reprojection-on
 With N > 1 the window is landmark-sharded over the ranks (contiguous CSR ranges); the reduced pose system and 8 scalars are
 all-reduced with RCCL once per linearization / back-substitution -> "scaling": "strong".  `value` is the metric's window
 (10 KF x 1000 landmarks) at every N; the window north_star states the multi-GPU target on, 10 KF x 50 000 landmarks, is the
-`scaling_window` object of every line (sharded like the headline; for N > 1 with the same window's unsharded rate on rank 0
-from the same run and the ratio of the two).
+`scaling_window` object of every `--full` line (sharded like the headline; for N > 1 with the same window's unsharded rate on
+rank 0 from the same run and the ratio of the two).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the line: `ms_per_step` is the
+wall time of one timed step, `value` the headline rate of those steps.  The objects below are null unless `--full` is given
+(the --no-* options switch single legs of a --full run off).
+
+--dump-outputs DIR  after the timed steps: what the last timed solve left in HBM, read back as a caller of the resident path
+                receives it (pvio_hip_ba_download + the summary), as DIR/<name>.npy in float64 -- frame_state (N x 16),
+                lm_inv_depth, lm_quality, lm_valid (all landmarks, gathered over the ranks), summary (num_iterations,
+                num_successful_steps, initial_cost, final_cost, termination, is_usable).  The window is seeded: the same
+                arguments give the same inputs on every run.
+
+Extra objects on the JSON line (--full):
   roofline      the kernel that moves the window's data (k_linearize): algorithmic bytes per launch / its average
                 duration, measured here with hipEvents on the solver's own stream (pvio_hip_ba_profile_resident), against the 8 TB/s
                 HBM peak; `traffic` = HBM bytes per launch from rocprofv3 counter passes run as children of THIS run (null
@@ -142,6 +153,36 @@ def build_window(args, preintegrate):
     from pvio_amd import synth
     n, m, vio = parse_workload(args.workload)
     return synth.make_window(n_frames=n, n_landmarks=m, use_inertial=vio, preintegrate=preintegrate if vio else None), (n, m, vio)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ctx, pb, sm, rank, dist):
+    """--dump-outputs: the states the last timed solve produced (downloaded from the resident buffers) and its summary, float64 .npy files.
+    Sharded runs gather the landmark arrays of every rank (contiguous CSR ranges, rank order) on rank 0.  Windows whose landmark arrays
+    would exceed DUMP_LIMIT_BYTES write a fixed seeded sample of the landmarks and its indices (`lm_index`)."""
+    from pvio_amd import BAState
+    st = ctx.download(BAState(pb))
+    lm = [st.lm_inv_depth, st.lm_quality, st.lm_valid.astype(np.float64)]
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, lm)
+        lm = [np.concatenate([p[i] for p in parts]) for i in range(3)]
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"frame_state": st.frame_state.astype(np.float64),
+              "summary": np.array([sm.num_iterations, sm.num_successful_steps, sm.initial_cost, sm.final_cost, sm.termination, sm.is_usable], np.float64)}
+    n_lm = len(lm[0])
+    keep = max(1, (DUMP_LIMIT_BYTES - 8 * arrays["frame_state"].size - 1024) // (8 * 4))
+    if n_lm > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n_lm, size=keep, replace=False))
+        lm = [a[idx] for a in lm]
+        arrays["lm_index"] = idx.astype(np.float64)
+    arrays.update(lm_inv_depth=lm[0], lm_quality=lm[1], lm_valid=lm[2])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def bench_klt(ctx, args, width=512, height=512, n_points=1500, reps=50):
@@ -365,6 +406,54 @@ def bench_scaling_window(ctx, args, rank, world, dist, barrier, preintegrate, n_
     return out
 
 
+def bench_roofline(ctx, pb, args, sharded, n_frames, n_lm, vio):
+    """roofline / roofline_dense objects of the line (--full): per-kernel durations of the resident solve and the counter passes."""
+    from pvio_amd import BASummary, synth
+    # ---- roofline leg: per-kernel durations from hipEvents on the solver's stream ----
+    prof = ctx.profile_resident(BASummary(pb, trace=False))
+    prof = ctx.profile_resident(BASummary(pb, trace=False))
+    alg_bytes = synth.algorithmic_bytes_per_iteration(pb)
+    lin_ms, lin_n = prof["k_linearize"]
+    avg_s = (lin_ms / max(lin_n, 1)) * 1e-3
+    achieved = alg_bytes / avg_s / 1e9 if avg_s > 0 else 0.0
+    roofline = {
+        "bound": "hbm", "kernel": "k_linearize", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic("k_linearize", args),
+        "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": avg_s * 1e6,
+        "kernel_us": {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in prof.items()},
+        "kernel_us_what": "hipEvents on the solver's stream around EAGER launches (one slot at a time, host synchronization per slot): their sum exceeds "
+                          "device_ms_per_step / slots, which is a hipGraph replay; kernel_us_rocprof = the same kernels inside graph replays",
+        "exchange_us": {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in ctx.last_comm.items()} if sharded else None,
+        "note": "working set < 1 MB: L2/Infinity-Cache resident, the iteration is launch/dependency-latency bound",
+    }
+    # the roofline above is for the kernel that moves the window's data (SURVEY 8d's per-iteration bytes); by DURATION the
+    # longest launch of a small window is the one-workgroup dense solve, a serial FP64 chain with no bandwidth or matrix-core
+    # roofline worth quoting (P^3/3 flops in its time is < 0.1 % of the FP64 peak)
+    roofline["longest_kernel"] = max(roofline["kernel_us"], key=roofline["kernel_us"].get)
+    roofline["traffic_source"] = _PMC["note"]
+    if _PMC.get("stats"):  # rocprofv3 --kernel-trace --stats child pass of this run (graph replays): what profiles/*kernel_stats*.csv holds
+        roofline["kernel_us_rocprof"] = {k: v["avg_us"] for k, v in _PMC["stats"].items() if k in roofline["kernel_us"]}
+        lin_r = _PMC["stats"].get("k_linearize")
+        if lin_r:
+            roofline["achieved_rocprof"] = alg_bytes / (lin_r["avg_us"] * 1e-6) / 1e9
+            roofline["frac_rocprof"] = roofline["achieved_rocprof"] / HBM_PEAK_GBS
+    # the dense kernel against the only roofline it has, FP64 arithmetic: P^3 / 3 + 2 P^2 flops (Cholesky of the reduced system with the
+    # right-hand side carried along + back substitution) per FACTORING launch.  Its average duration over all launches of a solve
+    # (rejected steps do not factor) is a lower bound of a factoring launch's: the fraction quoted is an upper bound -- and still
+    # ~1e-4: one workgroup on one CU, a chain of P dependent pivots (profiles/NOTES_r1_r3.md section 4).
+    Pd = (15 if vio else 6) * n_frames
+    dense_flops = Pd ** 3 / 3.0 + 2.0 * Pd ** 2
+    dense_s = roofline["kernel_us"]["k_dense"] * 1e-6
+    roofline_dense = {"bound": "mfma", "kernel": "k_dense", "achieved": dense_flops / dense_s / 1e12 if dense_s > 0 else 0.0, "peak": FP64_PEAK_TFLOPS,
+                      "unit": "TFLOP/s", "frac": (dense_flops / dense_s / 1e12) / FP64_PEAK_TFLOPS if dense_s > 0 else 0.0,
+                      "traffic": pmc_traffic("k_dense", args), "flops_per_factoring_launch": dense_flops, "avg_launch_us": dense_s * 1e6,
+                      "note": "dtype f64 on the FP64 matrix cores (v_mfma_f64_16x16x4_f64) + FP64 VALU; one workgroup: a serial dependency chain, not a throughput kernel"}
+    if n_lm >= 10000:
+        roofline["note"] = ("large window: k_linearize is FP64-issue bound (factor evaluation on the VALU + Schur complement on the f64 matrix "
+                            "cores), not HBM bound; see profiles/NOTES_r1_r3.md section 5")
+    return roofline, roofline_dense
+
+
 def relaunch_command(n, argv):
     """argv of the one-rank-per-GPU launch of this script (the form the driver uses for N > 1)"""
     port = os.environ.get("MASTER_PORT", str(29500 + os.getpid() % 2000))
@@ -387,6 +476,11 @@ def main():
                     help="diagnostics: run the multi-GPU code path (process group, RCCL communicator, eager launches, all-reduces) with "
                          "however many ranks there are, also one")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (roofline.traffic: null)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: API rate, candidate reuse, roofline and counter passes, scaling window, CPU "
+                         "baselines, KLT, concurrent windows, the reference's window (N > 1: the unsharded single-GPU rate)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed solve's states and summary as DIR/<name>.npy (float64)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.pmc_child:
@@ -437,7 +531,7 @@ def main():
     # same window's unsharded rate on rank 0 measured in the same run (`single_gpu_same_run`) and the ratio of the two.
     pb_full, (n_frames, n_lm, vio) = build_window(args, preintegrate)
     single_gpu = None
-    if world > 1:
+    if world > 1 and args.full:
         if rank == 0:
             c1 = HipContext(device=local_rank, use_graph=not args.no_graph)
             c1.upload(pb_full)
@@ -490,11 +584,14 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, pb, sm, rank, dist)
 
+    # ---- everything below the headline runs with --full only ----
     # ---- "API" rate: complete solves as the tracker issues them -- upload of the window (H2D), the iterations, the
     # states read back (D2H) -- next to the resident rate above ----
     api = None
-    if rank == 0 and world == 1 and not args.force_sharded:
+    if args.full and rank == 0 and world == 1 and not args.force_sharded:
         n_api = max(10, min(args.steps, 100))
         # The C-ABI call is what is timed -- what a compiled caller (the BundleAdjustor adapter) pays.  The ctypes structs are built once and the
         # state arrays are reset outside the timed region: building them per call is ~70 us of Python, none of it the product's
@@ -535,7 +632,7 @@ def main():
     # Same iterations, records and results; the window's last four iterations re-evaluate one rejected point (|gn| << radius), three of the
     # evaluations are saved.  Reported because it is what the host adapter runs by default -- the reference's keyframe solves consist of such runs.
     reuse = None
-    if rank == 0 and world == 1 and not args.force_sharded:
+    if args.full and rank == 0 and world == 1 and not args.force_sharded:
         try:
             c2 = HipContext(device=local_rank, use_graph=not args.no_graph, reuse_identical_candidates=True)
             c2.upload(pb)
@@ -556,59 +653,20 @@ def main():
         except Exception as e:
             reuse = {"error": repr(e)}
 
-    # ---- roofline leg: per-kernel durations from hipEvents on the solver's stream ----
-    prof = ctx.profile_resident(BASummary(pb, trace=False))
-    prof = ctx.profile_resident(BASummary(pb, trace=False))
-    alg_bytes = synth.algorithmic_bytes_per_iteration(pb)
-    lin_ms, lin_n = prof["k_linearize"]
-    avg_s = (lin_ms / max(lin_n, 1)) * 1e-3
-    achieved = alg_bytes / avg_s / 1e9 if avg_s > 0 else 0.0
-    roofline = {
-        "bound": "hbm", "kernel": "k_linearize", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic("k_linearize", args),
-        "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": avg_s * 1e6,
-        "kernel_us": {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in prof.items()},
-        "kernel_us_what": "hipEvents on the solver's stream around EAGER launches (one slot at a time, host synchronization per slot): their sum exceeds "
-                          "device_ms_per_step / slots, which is a hipGraph replay; kernel_us_rocprof = the same kernels inside graph replays",
-        "exchange_us": {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in ctx.last_comm.items()} if sharded else None,
-        "note": "working set < 1 MB: L2/Infinity-Cache resident, the iteration is launch/dependency-latency bound",
-    }
-    # the roofline above is for the kernel that moves the window's data (SURVEY 8d's per-iteration bytes); by DURATION the
-    # longest launch of a small window is the one-workgroup dense solve, a serial FP64 chain with no bandwidth or matrix-core
-    # roofline worth quoting (P^3/3 flops in its time is < 0.1 % of the FP64 peak)
-    roofline["longest_kernel"] = max(roofline["kernel_us"], key=roofline["kernel_us"].get)
-    roofline["traffic_source"] = _PMC["note"]
-    if _PMC.get("stats"):  # rocprofv3 --kernel-trace --stats child pass of this run (graph replays): what profiles/*kernel_stats*.csv holds
-        roofline["kernel_us_rocprof"] = {k: v["avg_us"] for k, v in _PMC["stats"].items() if k in roofline["kernel_us"]}
-        lin_r = _PMC["stats"].get("k_linearize")
-        if lin_r:
-            roofline["achieved_rocprof"] = alg_bytes / (lin_r["avg_us"] * 1e-6) / 1e9
-            roofline["frac_rocprof"] = roofline["achieved_rocprof"] / HBM_PEAK_GBS
-    # the dense kernel against the only roofline it has, FP64 arithmetic: P^3 / 3 + 2 P^2 flops (Cholesky of the reduced system with the
-    # right-hand side carried along + back substitution) per FACTORING launch.  Its average duration over all launches of a solve
-    # (rejected steps do not factor) is a lower bound of a factoring launch's: the fraction quoted is an upper bound -- and still
-    # ~1e-4: one workgroup on one CU, a chain of P dependent pivots (profiles/NOTES_r1_r3.md section 4).
-    Pd = (15 if vio else 6) * n_frames
-    dense_flops = Pd ** 3 / 3.0 + 2.0 * Pd ** 2
-    dense_s = roofline["kernel_us"]["k_dense"] * 1e-6
-    roofline_dense = {"bound": "mfma", "kernel": "k_dense", "achieved": dense_flops / dense_s / 1e12 if dense_s > 0 else 0.0, "peak": FP64_PEAK_TFLOPS,
-                      "unit": "TFLOP/s", "frac": (dense_flops / dense_s / 1e12) / FP64_PEAK_TFLOPS if dense_s > 0 else 0.0,
-                      "traffic": pmc_traffic("k_dense", args), "flops_per_factoring_launch": dense_flops, "avg_launch_us": dense_s * 1e6,
-                      "note": "dtype f64 on the FP64 matrix cores (v_mfma_f64_16x16x4_f64) + FP64 VALU; one workgroup: a serial dependency chain, not a throughput kernel"}
-    if n_lm >= 10000:
-        roofline["note"] = ("large window: k_linearize is FP64-issue bound (factor evaluation on the VALU + Schur complement on the f64 matrix "
-                            "cores), not HBM bound; see profiles/NOTES_r1_r3.md section 5")
+    roofline = roofline_dense = None
+    if args.full:
+        roofline, roofline_dense = bench_roofline(ctx, pb, args, sharded, n_frames, n_lm, vio)
 
     # ---- scaling window: the window north_star's multi-GPU sentence names (10 KF x 50 000 landmarks, full factor set),
     # sharded exactly like the headline window, same context and communicator; a few solves, barrier-bracketed ----
     scaling_window = None
-    if not args.no_scaling_window and args.workload in ("vio", "vision"):
+    if args.full and not args.no_scaling_window and args.workload in ("vio", "vision"):
         try:
             scaling_window = bench_scaling_window(ctx, args, rank, world, dist, barrier, preintegrate)
         except Exception as e:  # the headline line must still be printed
             scaling_window = {"error": repr(e)}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle_py as O
         O.build()
 
@@ -637,15 +695,15 @@ def main():
 
     # ---- KLT leg (second half of BASELINE.json's metric): tracks/ms, pyramids resident, TUM-VI-sized frames ----
     klt = None
-    if rank == 0 and world == 1 and not args.no_klt:
+    if args.full and rank == 0 and world == 1 and not args.no_klt:
         klt = bench_klt(ctx, args)
 
     multi = None
-    if rank == 0 and world == 1 and not args.no_klt:
+    if args.full and rank == 0 and world == 1 and not args.no_klt:
         multi = bench_concurrent_windows(pb_full)
 
     ref_window = None
-    if rank == 0 and world == 1 and not args.no_klt and args.workload == "vio":
+    if args.full and rank == 0 and world == 1 and not args.no_klt and args.workload == "vio":
         try:
             ref_window = bench_reference_window(preintegrate, cpu_seconds=0.0 if args.no_cpu_baseline else 2.0)
         except Exception as e:  # the headline line must still be printed

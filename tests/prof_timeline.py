@@ -1,6 +1,6 @@
 """Timeline of a graph-replayed solve from a rocprofv3 kernel trace: per kernel the in-kernel duration and the gap to the previous
 kernel's end, averaged over the solves of the run, factoring and non-factoring k_dense launches apart.
-usage (GPU box):  cd /tmp && rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -- python $REPO/bench.py --steps 30 --warmup 5 --no-klt --no-cpu-baseline --no-scaling-window --no-pmc
+usage (on an MI355X):  cd /tmp && rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -- python $REPO/bench.py --full --steps 30 --warmup 5 --no-klt --no-cpu-baseline --no-scaling-window --no-pmc
                   python tests/prof_timeline.py /tmp/tl"""
 import csv, glob, os, re, sys
 from collections import defaultdict

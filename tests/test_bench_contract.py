@@ -1,9 +1,13 @@
 """bench.py's host-side helpers (no GPU): workload names, the algorithmic-bytes figure of SURVEY section 8(d), and the rule that
-`roofline.traffic` is only printed from a PMC summary that was collected on exactly the kernel sources in the tree."""
+`roofline.traffic` is only printed from a PMC summary that was collected on exactly the kernel sources in the tree; what a plain run
+does next to --full, and --dump-outputs (one GPU test runs the plain line)."""
 import json
 import os
 import shutil
 import sys
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -88,3 +92,100 @@ def test_bare_multi_gpu_invocation_becomes_a_one_rank_per_gpu_launch(monkeypatch
     assert "does not match WORLD_SIZE" in str(e.value)
     src = inspect.getsource(bench.main)
     assert '"n_gpus": world' in src and '"n_gpus": args.gpus' not in src
+
+
+def _fake_solved(pb):
+    """what bench.dump_outputs needs of a context and a summary, without a GPU: download() fills the state the way the library does"""
+    class Ctx:
+        def download(self, st):
+            st.frame_state += 0.5
+            st.lm_inv_depth *= 2.0
+            st.lm_quality[:] = np.arange(len(st.lm_quality), dtype=np.float64)
+            st.lm_valid[::3] = 0
+            return st
+
+    class Summary:
+        num_iterations, num_successful_steps, initial_cost, final_cost, termination, is_usable = 7, 5, 12.5, 0.25, 1, 1
+    return Ctx(), Summary()
+
+
+def test_dump_outputs_writes_the_states_and_summary_as_float64(tmp_path):
+    """--dump-outputs: the arrays a caller of the resident path receives (download + summary), float64 .npy, the landmarks complete"""
+    pb = synth.make_window(n_frames=4, n_landmarks=30, use_inertial=False)
+    ctx, sm = _fake_solved(pb)
+    out = str(tmp_path / "out")
+    bench.dump_outputs(out, ctx, pb, sm, 0, None)
+    assert sorted(os.listdir(out)) == ["frame_state.npy", "lm_inv_depth.npy", "lm_quality.npy", "lm_valid.npy", "summary.npy"]
+    a = {n[:-4]: np.load(os.path.join(out, n)) for n in os.listdir(out)}
+    assert all(v.dtype == np.float64 for v in a.values())
+    np.testing.assert_array_equal(a["frame_state"], np.asarray(pb.frame_state, np.float64) + 0.5)
+    np.testing.assert_array_equal(a["lm_inv_depth"], 2.0 * np.asarray(pb.lm_inv_depth, np.float64))
+    assert a["lm_quality"].shape == a["lm_valid"].shape == (pb.n_landmarks,) and a["lm_valid"].sum() == pb.n_landmarks - len(range(0, 30, 3))
+    np.testing.assert_array_equal(a["summary"], [7, 5, 12.5, 0.25, 1, 1])
+    # rank != 0 of a run without a process group writes nothing
+    bench.dump_outputs(str(tmp_path / "r1"), ctx, pb, sm, 1, None)
+    assert not os.path.exists(str(tmp_path / "r1"))
+
+
+def test_dump_outputs_of_a_large_window_is_a_fixed_sample_within_the_limit(tmp_path, monkeypatch):
+    pb = synth.make_window(n_frames=4, n_landmarks=400, use_inertial=False)
+    limit = 8 * 4 * 16 + 8 * 4 * 100 + 1024  # frame_state + 100 landmarks x 4 arrays
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    dirs = []
+    for k in range(2):
+        ctx, sm = _fake_solved(pb)
+        dirs.append(str(tmp_path / ("d%d" % k)))
+        bench.dump_outputs(dirs[-1], ctx, pb, sm, 0, None)
+    total = sum(os.path.getsize(os.path.join(dirs[0], n)) - 128 for n in os.listdir(dirs[0]))  # .npy header: 128 bytes
+    assert total <= limit
+    idx = np.load(os.path.join(dirs[0], "lm_index.npy"))
+    assert len(idx) == 100 and (np.diff(idx) > 0).all()
+    np.testing.assert_array_equal(np.load(os.path.join(dirs[0], "lm_inv_depth.npy")), 2.0 * np.asarray(pb.lm_inv_depth)[idx.astype(int)])
+    for n in os.listdir(dirs[0]):
+        np.testing.assert_array_equal(np.load(os.path.join(dirs[0], n)), np.load(os.path.join(dirs[1], n)))
+
+
+def test_plain_run_is_the_headline_only():
+    """A plain run times the headline and prints it; every other leg runs behind --full (off by default)."""
+    import inspect
+    src = inspect.getsource(bench.main)
+    for call in ("bench_roofline(", "bench_scaling_window(", "bench_klt(", "bench_concurrent_windows(", "bench_reference_window(",
+                 "O.build()", "lib.pvio_hip_ba_solve(", "reuse_identical_candidates=True"):
+        head = src[:src.index(call)]
+        guard = head[head.rindex("\n    if "):]
+        assert "args.full" in guard, call
+    ap_src = src[src.index('"--full"'):]
+    assert 'action="store_true"' in ap_src.split("\n")[0]
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_one_line_and_dumps_the_same_outputs_twice(tmp_path):
+    """bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR on the GPU: one JSON line with the headline fields and K steps,
+    the --full objects null, float64 outputs; two runs with the same arguments write the same arrays."""
+    import subprocess
+    lines, dirs = [], []
+    for k in range(2):
+        dirs.append(str(tmp_path / ("run%d" % k)))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", dirs[-1]], cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        out = r.stdout.decode().strip().splitlines()
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    assert d["metric"] == "BA iterations/sec" and d["unit"] == "iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert abs(d["value"] - d["iterations_per_solve"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for k in ("api", "identical_candidate_reuse", "roofline", "roofline_dense", "cpu_baseline", "klt", "concurrent_windows", "scaling_window", "reference_window"):
+        assert d[k] is None, k
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["frame_state.npy", "lm_inv_depth.npy", "lm_quality.npy", "lm_valid.npy", "summary.npy"]
+    assert sum(os.path.getsize(os.path.join(dirs[0], n)) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(os.path.join(dirs[0], n)), np.load(os.path.join(dirs[1], n))
+        assert a.dtype == np.float64
+        np.testing.assert_array_equal(a, b)
+    summary = np.load(os.path.join(dirs[0], "summary.npy"))
+    assert summary[0] == d["iterations_per_solve"] and summary[3] == d["final_cost"]
+    assert np.load(os.path.join(dirs[0], "frame_state.npy")).shape == (10, 16)
+    assert np.load(os.path.join(dirs[0], "lm_inv_depth.npy")).shape == (1000,)
