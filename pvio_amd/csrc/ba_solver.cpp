@@ -938,6 +938,46 @@ static bool lu_inverse15(const double *Ain, double *inv) { // Eigen's .inverse()
     return true;
 }
 
+// The landmarks of the window that the victim observes (anchor or target), in their order, with their CSR rows, multiplicities and inverse depths.
+// false (nothing written) when the landmark arrays are not a window upload() accepts: the caller then passes the whole window on, to be rejected.
+static bool marg_subset(const pvio_ba_problem *pb, const pvio_ba_state *st, int victim, std::vector<int32_t> &anchor, std::vector<double> &anchor_z,
+                        std::vector<int32_t> &ptr, std::vector<int32_t> &frame, std::vector<double> &z, std::vector<int32_t> &mult, std::vector<double> &rho) {
+    const int N = pb->n_frames, M = pb->n_landmarks, F = pb->n_obs;
+    if (N < 1 || N > kMaxFrames || M < 0 || F < 0) return false;
+    if (M > 0 && (!st->lm_inv_depth || !pb->lm_anchor_frame || !pb->lm_anchor_z || !pb->lm_obs_ptr)) return false;
+    if (F > 0 && (!pb->obs_frame || !pb->obs_z)) return false;
+    if (M == 0 || pb->lm_obs_ptr[0] != 0 || pb->lm_obs_ptr[M] != F) return false;
+    std::vector<uint8_t> keep((size_t)M, 0);
+    size_t n_keep = 0, f_keep = 0;
+    for (int l = 0; l < M; ++l) {
+        const int b = pb->lm_obs_ptr[l], e = pb->lm_obs_ptr[l + 1], a = pb->lm_anchor_frame[l];
+        if (b < 0 || e < b || e > F || a < 0 || a >= N) return false;
+        if (pb->lm_multiplicity && pb->lm_multiplicity[l] < 1) return false;
+        uint32_t seen = 0;
+        for (int o = b; o < e; ++o) {
+            const int t = pb->obs_frame[o];
+            if (t < 0 || t >= N || t == a || (seen & (1u << t))) return false;
+            seen |= 1u << t;
+        }
+        if (a == victim || ((seen >> victim) & 1u)) keep[(size_t)l] = 1, ++n_keep, f_keep += (size_t)(e - b);
+    }
+    anchor.clear(), anchor_z.clear(), frame.clear(), z.clear(), mult.clear(), rho.clear();
+    // (+ 1: a victim without landmarks still hands upload() arrays, not null pointers)
+    anchor.reserve(n_keep + 1), anchor_z.reserve(2 * n_keep + 2), rho.reserve(n_keep + 1), frame.reserve(f_keep + 1), z.reserve(2 * f_keep + 2), mult.reserve(n_keep + 1);
+    ptr.assign(1, 0);
+    for (int l = 0; l < M; ++l) {
+        if (!keep[(size_t)l]) continue;
+        const int b = pb->lm_obs_ptr[l], e = pb->lm_obs_ptr[l + 1];
+        anchor.push_back(pb->lm_anchor_frame[l]);
+        anchor_z.push_back(pb->lm_anchor_z[2 * (size_t)l]), anchor_z.push_back(pb->lm_anchor_z[2 * (size_t)l + 1]);
+        rho.push_back(st->lm_inv_depth[l]);
+        if (pb->lm_multiplicity) mult.push_back(pb->lm_multiplicity[l]);
+        for (int o = b; o < e; ++o) frame.push_back(pb->obs_frame[o]), z.push_back(pb->obs_z[2 * (size_t)o]), z.push_back(pb->obs_z[2 * (size_t)o + 1]);
+        ptr.push_back((int32_t)frame.size());
+    }
+    return true;
+}
+
 // BundleAdjustor::marginalize_frame (bundle_adjustor.cpp:348-599).  The O(F) part -- un-robustified J^T J / J^T r of
 // every reprojection factor of the victim's landmarks, the scalar landmark elimination, the prior and the two IMU
 // factors -- runs on the GPU through k_linearize (MODE_MARG) + k_reduce; the 15N-dimensional dense tail (victim block
@@ -952,7 +992,20 @@ int BASolver::marginalize(const pvio_ba_problem *pb, const pvio_ba_state *st, in
     const auto tm0 = std::chrono::steady_clock::now();
     pvio_ba_problem p2 = *pb;
     p2.use_inertial = 1;
-    int rc = upload(&p2, st, /*may_return_early=*/true); // (this call synchronizes below, before the caller's arrays can change)
+    // :453-461: the problem is built from the tracks the victim observes (as their anchor or as a target) and from nothing else -- the other tracks
+    // are never evaluated, so whatever they hold (a zero or non-finite inverse depth, a point behind a camera) cannot reach the prior.  The kernels get
+    // those landmarks only.  (A window that upload() would reject is passed on whole, so that it is rejected for the same reason.)
+    pvio_ba_state st2 = *st;
+    std::vector<int32_t> k_anchor, k_ptr, k_frame, k_mult;
+    std::vector<double> k_anchor_z, k_z, k_rho;
+    if (marg_subset(pb, st, victim, k_anchor, k_anchor_z, k_ptr, k_frame, k_z, k_mult, k_rho)) {
+        p2.n_landmarks = (int32_t)k_anchor.size(), p2.n_obs = (int32_t)k_frame.size();
+        p2.lm_anchor_frame = k_anchor.data(), p2.lm_anchor_z = k_anchor_z.data(), p2.lm_obs_ptr = k_ptr.data();
+        p2.obs_frame = k_frame.data(), p2.obs_z = k_z.data();
+        p2.lm_multiplicity = pb->lm_multiplicity ? k_mult.data() : nullptr;
+        st2.lm_inv_depth = k_rho.data();
+    }
+    int rc = upload(&p2, &st2, /*may_return_early=*/true); // (this call synchronizes below, before the caller's arrays can change)
     if (rc != PVIO_OK) return rc;
     const auto tm1 = std::chrono::steady_clock::now();
     const Dims &dm = v_.dm;

@@ -127,7 +127,9 @@ void PVBA_EIG_FN(const double *A, int n, double *__restrict w, double *__restric
     for (int l = 0; l < n; ++l) {
         tst1 = std::fmax(tst1, std::fabs(w[l]) + std::fabs(e[l]));
         int m = l;
-        while (m < n) {
+        // (e[n - 1] is 0 on finite input and ends the scan there; a NaN in it -- 0 x NaN from a rotation of a non-finite matrix -- fails
+        // every test, and m = n would read w[n] and write e[n] below: the scan stops at n - 1 on its own)
+        while (m < n - 1) {
             if (std::fabs(e[m]) <= eps * tst1) break;
             ++m;
         }

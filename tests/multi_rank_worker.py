@@ -34,6 +34,8 @@ def main():
         return 0
 
     lib.hipemu_set_allreduce(allreduce)
+    if case.endswith("@marg"):
+        return marginalize_only(out_dir, case.split("@")[0], linearize_mode, [int(x) for x in sys.argv[4].split(",")], lib, rank, world)
     graph = case.endswith("@graph")  # resident re-solves through the slot GRAPH: both collectives of an iteration captured in it, > 1 rank
     timeout = case.endswith("@timeout")  # a time limit that only ONE rank's clock exceeds (PVIO_HIP_DEBUG_TIMEOUT_RANK): nobody may hang
     case = case.split("@")[0]
@@ -71,6 +73,35 @@ def main():
              iters=sm.num_iterations, term=sm.termination, costs=np.array([t["cost"] for t in sm.trace()]),
              succ=np.array([t["step_is_successful"] for t in sm.trace()]), gmax=np.array([t["gradient_max_norm"] for t in sm.trace()]), **marg, **graph_info)
     dist.barrier()
+    dist.destroy_process_group()
+
+
+def marginalize_only(out_dir, case, linearize_mode, victims, lib, rank, world):
+    """marginalize_frame of every victim on this rank's landmark shard of ONE state: the window solved (unsharded) by the oracle, with a regular
+    old prior over frames 0 .. N-2 -- what the test compares with oracle.marginalize on the whole window"""
+    import ctypes as C
+
+    import marg_compare
+    from oracle import oracle_py as O
+    from pvio_amd import BAState
+    from pvio_amd.solver import HipContext
+    pb, st = marg_compare.sharded_window(O, case)
+    shard = pb.shard(rank, world)
+    l0, l1 = shard.meta["lm_range"] if world > 1 else (0, pb.n_landmarks)
+    sst = BAState(shard)
+    sst.frame_state[:] = st.frame_state
+    sst.lm_inv_depth = np.ascontiguousarray(st.lm_inv_depth[l0:l1])
+    ctx = HipContext(lib=lib, rank=rank, world_size=world, use_graph=False, linearize_mode=linearize_mode)
+    uid = (C.c_uint8 * 128)()
+    assert lib.pvio_hip_comm_unique_id(uid) == 0
+    assert lib.pvio_hip_comm_init(ctx.ctx, uid, rank, world) == 0
+    out = {}
+    for v in victims:
+        S, s_, IM, iv = ctx.marginalize(shard, sst, v)
+        out.update({"S_%d" % v: S, "s_%d" % v: s_, "IM_%d" % v: IM, "iv_%d" % v: iv})
+    np.savez(os.path.join(out_dir, "rank%d.npz" % rank), l0=l0, l1=l1, **out)
+    dist.barrier()
+    ctx.close()
     dist.destroy_process_group()
 
 

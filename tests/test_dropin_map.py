@@ -124,12 +124,29 @@ def _solved(oracle, **kw):
     return pb, st
 
 
-def diff_marginalize(ref, drop, oracle, victim, regular_prior):  # noqa: F811
-    """BundleAdjustor().marginalize_frame(map, victim) + compute_reprojection_error(map) through both libraries"""
+def _marg_window(oracle, regular_prior, window):
     import marg_compare
-    pb, st = marg_compare.solved_window(oracle, regular_prior=regular_prior, n_frames=8, n_landmarks=200, use_inertial=True, visibility=5)
+    if window.get("use_inertial"):
+        return marg_compare.solved_window(oracle, regular_prior=regular_prior, **window)
+    # no IMU factor: a prior over every frame (set after the solve) keeps the victim's 15 x 15 block regular
+    pb, st = marg_compare.solved_window(oracle, **window)
+    marg_compare.set_regular_prior(pb, np.arange(pb.n_frames))
+    return pb, st
+
+
+def _invalidate(tracks, invalid):
+    """TF_VALID cleared on the tracks `invalid` (indices into the track table): the adapter's flattening drops them (host/bundle_adjustor.cpp)"""
+    for k in invalid:
+        tracks.valid[k] = 0
+
+
+def diff_marginalize(ref, drop, oracle, victim, regular_prior, window=None, invalid=()):  # noqa: F811
+    """BundleAdjustor().marginalize_frame(map, victim) + compute_reprojection_error(map) through both libraries"""
+    window = window or dict(n_frames=8, n_landmarks=200, use_inertial=True, visibility=5)
+    pb, st = _marg_window(oracle, regular_prior, window)
     ta, _ = ref.tracks_of_problem(pb, inv_depth=st.lm_inv_depth)
     tb, _ = ref.tracks_of_problem(pb, inv_depth=st.lm_inv_depth)
+    _invalidate(ta, invalid), _invalidate(tb, invalid)
     Sa, sa, IMa, iva = ref.reference().marginalize(pb, st.frame_state, ta, victim)
     Sb, sb, IMb, ivb = drop.marginalize(pb, st.frame_state, tb, victim)
     scale = np.abs(IMa).max()
@@ -146,12 +163,13 @@ def test_emulated_dropin_marginalize_on_reference_map(ref, emu, oracle, victim):
     print(diff_marginalize(ref, emu, oracle, victim, regular_prior=(victim != 0)))
 
 
-def diff_cycle(ref, drop, oracle, **kw):  # noqa: F811
+def diff_cycle(ref, drop, oracle, invalid=(), **kw):  # noqa: F811
     """the keyframe cycle on ONE Map: Map::marginalize_frame(0) (the reference's own caller, map.cpp:73-88, which erases the victim and
     re-anchors its tracks) and then BundleAdjustor().solve of the frames left with the prior just made (sliding_window_tracker.cpp:91-113)"""
     pb, st = _solved(oracle, **kw)
     ta, _ = ref.tracks_of_problem(pb, inv_depth=st.lm_inv_depth)
     tb, _ = ref.tracks_of_problem(pb, inv_depth=st.lm_inv_depth)
+    _invalidate(ta, invalid), _invalidate(tb, invalid)
     fa, ua = ref.reference().marginalize_then_solve(pb, st.frame_state, ta, 0)
     fb, ub = drop.marginalize_then_solve(pb, st.frame_state, tb, 0)
     assert ua == ub
@@ -163,6 +181,34 @@ def diff_cycle(ref, drop, oracle, **kw):  # noqa: F811
 
 def test_emulated_dropin_keyframe_cycle_on_reference_map(ref, emu, oracle):  # noqa: F811
     print(diff_cycle(ref, emu, oracle, n_frames=7, n_landmarks=120, use_inertial=True, visibility=5))
+
+
+# marginalization of windows whose Map holds PLANE tracks (plane-distance factors; small planes = duplicate blocks) or tracks with TF_VALID
+# cleared: the adapter's flattening drops both from the prior (host/bundle_adjustor.cpp), the reference's marginalize_frame skips them
+MARG_PLANE_CASES = [("plane", 0), ("plane", 2), ("vio_plane", 0), ("vio_plane", 3), ("vio_small_planes", 0), ("vio_small_planes", 3)]
+INVALID_TRACKS = tuple(range(0, 200, 7))
+CYCLE_CASES = ["vio_plane", "vio_small_planes", "vio_invalid_tracks"]
+
+
+def _cycle_case(ref, drop, oracle, name):  # noqa: F811
+    if name == "vio_invalid_tracks":
+        return diff_cycle(ref, drop, oracle, invalid=tuple(range(0, 120, 7)), n_frames=7, n_landmarks=120, use_inertial=True, visibility=5)
+    return diff_cycle(ref, drop, oracle, **SOLVE_CASES[name])
+
+
+@pytest.mark.parametrize("name,victim", MARG_PLANE_CASES)
+def test_emulated_dropin_marginalize_planes_on_reference_map(ref, emu, oracle, name, victim):  # noqa: F811
+    print(diff_marginalize(ref, emu, oracle, victim, regular_prior=(victim != 0), window=SOLVE_CASES[name]))
+
+
+@pytest.mark.parametrize("victim", [0, 3])
+def test_emulated_dropin_marginalize_invalid_tracks_on_reference_map(ref, emu, oracle, victim):  # noqa: F811
+    print(diff_marginalize(ref, emu, oracle, victim, regular_prior=(victim != 0), invalid=INVALID_TRACKS))
+
+
+@pytest.mark.parametrize("name", CYCLE_CASES)
+def test_emulated_dropin_keyframe_cycle_edges_on_reference_map(ref, emu, oracle, name):  # noqa: F811
+    print(_cycle_case(ref, emu, oracle, name))
 
 
 def diff_pnp(ref, drop, oracle, use_inertial):  # noqa: F811
@@ -238,6 +284,24 @@ def test_gpu_dropin_marginalize_on_reference_map(ref, gpu, oracle, victim):  # n
 def test_gpu_dropin_keyframe_cycle_on_reference_map(ref, gpu, oracle):  # noqa: F811
     print(diff_cycle(ref, gpu, oracle, n_frames=7, n_landmarks=120, use_inertial=True, visibility=5))
     print(diff_cycle(ref, gpu, oracle, n_frames=10, n_landmarks=300, use_inertial=True, visibility=6))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,victim", MARG_PLANE_CASES)
+def test_gpu_dropin_marginalize_planes_on_reference_map(ref, gpu, oracle, name, victim):  # noqa: F811
+    print(diff_marginalize(ref, gpu, oracle, victim, regular_prior=(victim != 0), window=SOLVE_CASES[name]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("victim", [0, 3])
+def test_gpu_dropin_marginalize_invalid_tracks_on_reference_map(ref, gpu, oracle, victim):  # noqa: F811
+    print(diff_marginalize(ref, gpu, oracle, victim, regular_prior=(victim != 0), invalid=INVALID_TRACKS))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", CYCLE_CASES)
+def test_gpu_dropin_keyframe_cycle_edges_on_reference_map(ref, gpu, oracle, name):  # noqa: F811
+    print(_cycle_case(ref, gpu, oracle, name))
 
 
 def _random_window(oracle, seed):

@@ -54,6 +54,36 @@ def test_sharded_solve_matches_oracle(oracle, case, world, mode):
                 np.testing.assert_allclose(z["marg_iv"], iv0, rtol=1e-5, atol=1e-6 * np.abs(iv0).max())
 
 
+# marginalize_frame on landmark shards: every rank sums the victim's landmarks of its own range, the reduced buffer is all-reduced, and the replicated
+# terms (IMU factors, the old prior, the victim's rotation prior) are added once, after it.  Victims 0, 2 and N - 1, rotation priors on frames 1, 3, 4
+# of vio_rot_prior; four ranks over landmarks sorted by anchor: ranks that hold none of the victim's landmarks; both landmark roles.
+@pytest.mark.parametrize("case,world,mode,victims", [("vio_partial", 2, 1, (0, 2, 5)), ("vio_rot_prior", 3, 2, (0, 1, 2, 4)),
+                                                     ("vio_partial/by_anchor", 4, 1, (0, 2, 5)), ("vio_partial/by_anchor", 4, 2, (0, 2, 5))])
+def test_sharded_marginalize_matches_oracle(oracle, case, world, mode, victims):
+    import marg_compare
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hipemu"), "libpvio_hipemu.so"])
+    pb, st = marg_compare.sharded_window(oracle, case)
+    if case.endswith("/by_anchor"):
+        ptr = pb.lm_obs_ptr
+        sees = lambda v, l: pb.lm_anchor_frame[l] == v or (pb.obs_frame[ptr[l]:ptr[l + 1]] == v).any()  # noqa: E731
+        ranges = [pb.shard(r, world).meta["lm_range"] for r in range(world)]
+        assert any(not any(sees(v, l) for l in range(*lr)) for v in victims for lr in ranges)
+    with tempfile.TemporaryDirectory() as d:
+        port = 29500 + ((os.getpid() + 29 * world + mode) % 2000)
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
+               "--master-port", str(port), os.path.join(ROOT, "tests", "multi_rank_worker.py"), d, case + "@marg", str(mode), ",".join(map(str, victims))]
+        subprocess.run(cmd, check=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="1"), capture_output=True)
+        for v in victims:
+            expect = oracle.marginalize(pb, st, v)
+            for r in range(world):
+                z = np.load(os.path.join(d, "rank%d.npz" % r))
+                S, s_, IM, iv = z["S_%d" % v], z["s_%d" % v], z["IM_%d" % v], z["iv_%d" % v]
+                marg_compare.assert_finite_prior(S, s_, IM, iv, "rank %d victim %d" % (r, v))
+                np.testing.assert_allclose(IM, expect[2], rtol=1e-7, atol=1e-9 * np.abs(expect[2]).max())
+                np.testing.assert_allclose(iv, expect[3], rtol=1e-7, atol=1e-9 * np.abs(expect[3]).max())
+                np.testing.assert_allclose(S.T @ S, expect[0].T @ expect[0], rtol=1e-6, atol=1e-7 * np.abs(expect[2]).max())
+
+
 # (mode 2: the large-window landmark role on the shards -- what bench.py's sharded 10 KF x 50 000 leg runs inside the captured graph)
 @pytest.mark.parametrize("case,world,mode", [("vio_partial", 2, 0), ("vio_plane", 4, 0), ("config1_10x200", 8, 0), ("vio_partial", 2, 2), ("config1_10x200", 4, 2)])
 def test_sharded_graph_replay_with_captured_collectives(oracle, case, world, mode):

@@ -310,13 +310,22 @@ def test_solve_equals_reference(ref, oracle, kind):
     print("%s: %d iterations, per-iteration states within %.2e of the reference's solve" % (kind, sm.num_iterations, worst))
 
 
-@pytest.mark.parametrize("kind,victim", [("vio", 0), ("vio", 2), ("vio", 5), ("vio_zero_bias", 0)])
+# plane kinds: the reference's own marginalize_frame skips TF_PLANE tracks; small planes are duplicate blocks of VALID tracks, listed once (:455-510)
+@pytest.mark.parametrize("kind,victim", [("vio", 0), ("vio", 2), ("vio", 5), ("vio_zero_bias", 0),
+                                         ("plane", 0), ("plane", 2), ("vio_plane", 0), ("vio_plane", 3), ("vio_small_planes", 0), ("vio_small_planes", 3)])
 def test_marginalize_equals_reference(ref, oracle, kind, victim):
     """marginalize_frame -- bundle_adjustor.cpp:348-599: the information matrix / vector S^T S, S^T s of the new prior (eigenvector
     signs cancel) and the reprojection error pass (:321-336), after a solve"""
     pb = _window(kind, oracle)
     st, sm = BAState(pb), BASummary(pb)
     oracle.solve(pb, st, sm)
+    if not pb.use_inertial:  # no IMU factor: a prior over every frame keeps the victim's 15 x 15 block regular (the reference would invert a singular one)
+        rng = np.random.default_rng(5)
+        D = 15 * pb.n_frames
+        pb.prior_frames = np.arange(pb.n_frames, dtype=np.int32)
+        pb.prior_S = np.diag(10.0 ** rng.uniform(0.5, 3.0, D)) @ np.linalg.qr(rng.normal(size=(D, D)))[0]
+        pb.prior_s = rng.normal(size=D)
+        pb.prior_lin_state = pb.frame_state.copy()
     Sa, sa, IMa, iva = oracle.marginalize(pb, st, victim)
     trk, _ = ref.tracks_of_problem(pb, inv_depth=st.lm_inv_depth)
     Sb, sb, IMb, ivb = ref.marginalize(pb, st.frame_state, trk, victim)

@@ -83,3 +83,36 @@ def test_both_builds_are_bit_identical(name):
     wa, Va = _eig("generic", A)
     wb, Vb = _eig("avx2", A)
     assert (wa == wb).all() and (Va == Vb).all()
+
+
+_NONFINITE_CHILD = r'''
+import ctypes as C, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import test_sym_eig as T
+rng = np.random.default_rng(11)
+for build in sys.argv[2:]:
+    for n in (2, 3, 15, 30, 105):
+        for bad in (np.nan, np.inf):
+            B = rng.standard_normal((n, n))
+            A = B @ B.T
+            A[n // 2, :] = A[:, n // 2] = bad
+            w, Vt = T._eig(build, A)
+            assert not np.isfinite(w).all(), (build, n, bad)
+            junk = [bytearray(64 * k) for k in range(1, 200)]  # the allocator's own checks see a damaged heap
+print("ok")
+'''
+
+
+def test_sym_eig_keeps_in_bounds_on_a_non_finite_matrix():
+    """a NaN / inf in the matrix (a marginalization whose prior is poisoned by a non-finite factor, as the reference's would be) gives
+    non-finite eigenvalues and nothing else: the QL scan for a negligible off-diagonal element once ran past the end (m = n, an
+    out-of-bounds read of w and write of e) because no test on a NaN succeeds.  Run in a child so that a damaged heap fails this test only."""
+    import os
+    import subprocess
+    import sys
+    builds = ["generic", "dispatched"] + (["avx2"] if _has_avx2() else [])
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, "-c", _NONFINITE_CHILD, here] + builds, capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(here), os.environ.get("PYTHONPATH", "")])))
+    assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
