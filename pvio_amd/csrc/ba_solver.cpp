@@ -17,6 +17,7 @@
 
 namespace pvba {
 constexpr bool kDenseLookAheadDefault = true; // same-box A/B (profiles/r3_ab_lookahead.txt): 12 076 -> 12 678 iterations/s
+constexpr size_t kLinLdsBudget = 112 * 1024;  // bytes of LDS the chunks of k_linearize's plane and register-tile roles are sized for
 
 
 DevicePool::~DevicePool() { release(); }
@@ -88,6 +89,411 @@ void BASolver::invalidate_graph() {
     graph_slots_ = 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// upload = validate -> plan -> allocate -> stage -> commit.  validate and plan touch neither the device nor the solver;
+// from allocate's first pool request until commit the context is between windows (upload() itself says what that means).
+// ---------------------------------------------------------------------------------------------------------------------
+
+struct Reject { // a failed argument check: what upload() returns and reports
+    int code = PVIO_OK;
+    const char *msg = "";
+    int group = -1; // check_landmarks only: the run of upload's order of checks the failing one belongs to
+};
+
+// The checks of the landmark and observation arrays, shared with marg_subset.  validate_upload makes the other arrays' checks between them, in the
+// order upload() has always made them (the first failing check decides code and message), so a failure names its run: 0 the counts, 1 null arrays and
+// CSR ends, 2 the walk over the landmarks, 3 the multiplicities.  lm_seen[l], bit f: landmark l is observed in frame f (what the duplicate check
+// builds; View::lm_seen).  Needs pb and st only.
+static Reject check_landmarks(const pvio_ba_problem *pb, const pvio_ba_state *st, std::vector<uint32_t> &lm_seen) {
+    const int N = pb->n_frames, M = pb->n_landmarks, F = pb->n_obs;
+    if (N < 1 || N > kMaxFrames) return {PVIO_ERR_UNSUPPORTED, "n_frames must be in [1, 32]", 0};
+    if (M < 0 || F < 0 || (M > 0 && !st->lm_inv_depth)) return {PVIO_ERR_INVALID_ARGUMENT, "bad landmark arrays", 0};
+    if (M > 0 && (!pb->lm_anchor_frame || !pb->lm_anchor_z || !pb->lm_obs_ptr)) return {PVIO_ERR_INVALID_ARGUMENT, "null landmark array", 1};
+    if (F > 0 && (!pb->obs_frame || !pb->obs_z)) return {PVIO_ERR_INVALID_ARGUMENT, "null observation array", 1};
+    if (M > 0 && (pb->lm_obs_ptr[0] != 0 || pb->lm_obs_ptr[M] != F)) return {PVIO_ERR_INVALID_ARGUMENT, "lm_obs_ptr must start at 0 and end at n_obs", 1};
+    lm_seen.assign((size_t)std::max(M, 1), 0u);
+    int maxK = 1;
+    for (int l = 0; l < M; ++l) {
+        const int b = pb->lm_obs_ptr[l], e = pb->lm_obs_ptr[l + 1];
+        if (b < 0 || e < b || e > F) return {PVIO_ERR_INVALID_ARGUMENT, "lm_obs_ptr is not a valid CSR", 2};
+        const int a = pb->lm_anchor_frame[l];
+        if (a < 0 || a >= N) return {PVIO_ERR_INVALID_ARGUMENT, "anchor frame out of range", 2};
+        maxK = std::max(maxK, e - b);
+        uint32_t seen = 0;
+        for (int o = b; o < e; ++o) {
+            const int t = pb->obs_frame[o];
+            if (t < 0 || t >= N || t == a) return {PVIO_ERR_INVALID_ARGUMENT, "observation frame out of range or equal to the anchor", 2};
+            if (seen & (1u << t)) return {PVIO_ERR_UNSUPPORTED, "a landmark lists the same target frame twice", 2};
+            seen |= 1u << t;
+        }
+        lm_seen[(size_t)l] = seen;
+    }
+    if (maxK > kLinThreads) return {PVIO_ERR_UNSUPPORTED, "too many observations per landmark", 2};
+    if (pb->lm_multiplicity)
+        for (int l = 0; l < M; ++l)
+            if (pb->lm_multiplicity[l] < 1) return {PVIO_ERR_INVALID_ARGUMENT, "lm_multiplicity must be >= 1", 3};
+    return {};
+}
+
+// validate: every argument check of an upload.  No HIP call, nothing of the solver read or written.
+static Reject validate_upload(const pvio_ba_problem *pb, const pvio_ba_state *st, std::vector<uint32_t> &lm_seen) {
+    if (!pb || !st || !st->frame_state) return {PVIO_ERR_INVALID_ARGUMENT, "null problem/state"};
+    const Reject lm = check_landmarks(pb, st, lm_seen);
+    if (lm.group == 0) return lm;
+    const int N = pb->n_frames;
+    if (!pb->frame_fixed || !pb->cam_extrinsic || !pb->imu_extrinsic || !pb->sqrt_inv_cov || !pb->intrinsics) return {PVIO_ERR_INVALID_ARGUMENT, "null per-frame array"};
+    if (lm.group == 1) return lm;
+    if (pb->prior_n < 0 || pb->prior_n > N || pb->max_iterations < 0 || pb->n_plane_factors < 0) return {PVIO_ERR_INVALID_ARGUMENT, "negative count / prior_n > n_frames"};
+    if (pb->prior_n > 0 && (!pb->prior_frames || !pb->prior_S || !pb->prior_s || !pb->prior_lin_state)) return {PVIO_ERR_INVALID_ARGUMENT, "null prior array"};
+    if (pb->use_inertial && (!pb->preint_valid || !pb->preint_delta || !pb->preint_sqrt_inv_cov || !pb->preint_jacobian)) return {PVIO_ERR_INVALID_ARGUMENT, "null pre-integration array"};
+    if (pb->n_plane_factors > 0) {
+        if (!pb->plane_obs_ptr || !pb->plane_obs_frame || !pb->plane_obs_z || !pb->plane_normal || !pb->plane_distance) return {PVIO_ERR_INVALID_ARGUMENT, "null plane array"};
+        if (pb->plane_obs_ptr[0] != 0) return {PVIO_ERR_INVALID_ARGUMENT, "plane_obs_ptr must start at 0"};
+        for (int f = 0; f < pb->n_plane_factors; ++f) {
+            if (pb->plane_obs_ptr[f + 1] < pb->plane_obs_ptr[f]) return {PVIO_ERR_INVALID_ARGUMENT, "plane_obs_ptr is not a valid CSR"};
+            for (int o = pb->plane_obs_ptr[f]; o < pb->plane_obs_ptr[f + 1]; ++o)
+                if (pb->plane_obs_frame[o] < 0 || pb->plane_obs_frame[o] >= N) return {PVIO_ERR_INVALID_ARGUMENT, "plane observation frame out of range"};
+        }
+    }
+    if (lm.group == 2) return lm;
+    for (int i = 0; i < pb->prior_n; ++i)
+        if (pb->prior_frames[i] < 0 || pb->prior_frames[i] >= N) return {PVIO_ERR_INVALID_ARGUMENT, "prior frame out of range"};
+    if (pb->n_rot_priors < 0 || (pb->n_rot_priors > 0 && (!pb->rot_prior_frame || !pb->rot_prior_q0 || !pb->rot_prior_sqrt_info)))
+        return {PVIO_ERR_INVALID_ARGUMENT, "bad rotation prior arrays"};
+    uint32_t has_rot = 0;
+    for (int i = 0; i < pb->n_rot_priors; ++i) {
+        const int f = pb->rot_prior_frame[i];
+        if (f < 0 || f >= N) return {PVIO_ERR_INVALID_ARGUMENT, "rotation prior frame out of range"};
+        if (has_rot & (1u << f)) return {PVIO_ERR_UNSUPPORTED, "more than one rotation prior on a frame"};
+        has_rot |= 1u << f;
+    }
+    return lm; // the multiplicities' failure, or none
+}
+
+// Experiment switches of the planning (unsupported).  Read once per process, at the first upload that gets as far as its plan.
+struct UploadSwitches {
+    int lm_wgs;          // PVIO_HIP_LM_WGS=n caps the landmark workgroups of k_linearize (>= 1; the plan clamps it to 4 x CUs -- the partial-row buffers are sized
+                         // from the resulting grid, so any value in the range is safe; anything else is ignored)
+    bool fuse_off;       // PVIO_HIP_FUSE_BACKSUB=0: tests -- small windows through the separate k_backsub launch, i.e. the split-finalize form
+    int fuse_max;        // PVIO_HIP_FUSE_BACKSUB_MAX: experiments -- the landmark count up to which the back-substitution stays inside k_dense; clamped to 16 .. 4096
+    bool split_off;      // PVIO_HIP_SPLIT_FIN=0 keeps everything in k_dense (A/B timing, tests of both forms)
+    int dense_la;        // PVIO_HIP_DENSE_LA=0 / 1 overrides the default form of the register-resident factorization; -1: not set
+    bool img_scaled_off; // PVIO_HIP_IMG_SCALED=0: k_dense scales the image every time
+};
+static const UploadSwitches &upload_switches() {
+    static const UploadSwitches sw = [] {
+        auto env = [](const char *name, int unset) {
+            const char *s = std::getenv(name);
+            return s ? std::atoi(s) : unset;
+        };
+        UploadSwitches s;
+        s.lm_wgs = env("PVIO_HIP_LM_WGS", 0);
+        s.fuse_off = env("PVIO_HIP_FUSE_BACKSUB", 1) == 0;
+        s.fuse_max = std::min(4096, std::max(16, env("PVIO_HIP_FUSE_BACKSUB_MAX", 256)));
+        s.split_off = env("PVIO_HIP_SPLIT_FIN", 1) == 0;
+        s.dense_la = env("PVIO_HIP_DENSE_LA", -1);
+        s.img_scaled_off = env("PVIO_HIP_IMG_SCALED", 1) == 0;
+        return s;
+    }();
+    return sw;
+}
+
+// Everything an upload derives on the host.  Owns the derived arrays until the DMA has left: staging sends the large ones from where they lie.
+struct UploadPlan {
+    Dims dm{}; // complete (compared with memcmp, passed to every kernel)
+    std::vector<uint8_t> pose_active, motion_active, pre_valid, chunk_perm;
+    std::vector<int32_t> obs_lm, prior_slot, rot_slot, plane_chunk, chunk_lm, chunk_tptr, chunk_geo, tp_tile_dst, task_desc;
+    std::vector<uint32_t> lm_seen; // (validate's by-product)
+    std::vector<double> lm_mult;   // duplicate residual blocks (bundle_adjustor.cpp:165-179); empty: no landmark counts twice
+};
+
+// landmark ranges of <= lm_slots landmarks and <= 256 factors (one thread per factor), cut where the anchor frame changes if `one_anchor`
+static std::vector<int32_t> cut_chunks(const pvio_ba_problem *pb, int lm_slots, bool one_anchor) {
+    const int M = pb->n_landmarks;
+    std::vector<int32_t> chunk_lm(1, 0);
+    int cnt = 0, fac = 0;
+    for (int l = 0; l < M; ++l) {
+        const int k = pb->lm_obs_ptr[l + 1] - pb->lm_obs_ptr[l];
+        if (cnt > 0 && (cnt + 1 > lm_slots || fac + k > kLinThreads || (one_anchor && pb->lm_anchor_frame[l] != pb->lm_anchor_frame[l - 1]))) {
+            chunk_lm.push_back(l);
+            cnt = 0, fac = 0;
+        }
+        ++cnt, fac += k;
+    }
+    if (M > 0) chunk_lm.push_back(M);
+    return chunk_lm;
+}
+
+// Register-tile role.  A small window is latency-bound per workgroup, so chunks are sized to put one chunk on every CU (256 on MI355X) rather than to
+// fill the LDS; a larger one falls back to LDS-filling chunks that each workgroup walks in a grid-stride loop.
+// One workgroup fits on a CU (registers, LDS) and the IMU / prior workgroups are the longest: the landmark chunks get the CUs that are left, so that
+// the whole grid is resident at once instead of queueing a second round behind it.  One landmark chunk per free CU.  Round 5 measured the alternative
+// the 22x traffic of the partial rows suggests -- fewer, fatter workgroups, i.e. fewer rows for k_reduce to sum (PVIO_HIP_LM_WGS;
+// profiles/r5_ab_partials.txt): the traffic falls with the count and the iteration rate with it, because a workgroup's chain grows with the landmarks
+// it holds (the per-landmark sums and the tile accumulation walk them one after another): 48 rows = 12 161 against 14 112 iterations/s, k_linearize
+// 18.4 -> 29.2 us for 0.4 us less in k_reduce.
+static void plan_register_tile_chunks(const pvio_ba_problem *pb, int cus, int lm_wgs_cap, UploadPlan &pl) {
+    Dims &dm = pl.dm;
+    // (the cap may exceed the free CUs: more than one workgroup per CU where registers and LDS allow)
+    const int lm_cus = lm_wgs_cap > 0 ? lm_wgs_cap : std::max(1, cus - dm.G_plane - dm.G_pre - dm.G_prior);
+    const int slots_lds = (int)std::max<size_t>(1, std::min<size_t>(kLinLdsBudget / 8 / (40 * dm.N + 46), (size_t)kLinThreads));
+    dm.lm_slots = std::min(slots_lds, std::max(1, (dm.M + lm_cus - 1) / lm_cus));
+    pl.chunk_lm = cut_chunks(pb, dm.lm_slots, false);
+    dm.n_chunks = (int)pl.chunk_lm.size() - 1;
+    dm.G_lm = std::max(1, std::min(dm.n_chunks, lm_cus));
+}
+
+// scatter table of the Schur tiles' accumulator entries into the element-major 3 x 3-task partial row (the flush of ba_lin_tp.h): entry r of lane l of
+// tile (bi, bj) is element (16 bi + (l >> 4) + 4 r, 16 bj + (l & 15)) of the lower triangle
+static std::vector<int32_t> tp_tile_dst_table(int N, int P6) {
+    std::vector<int32_t> table;
+    const int nbt = tp_u_stride(P6) >> 4;
+    auto task_index = [&](int fi, int fj, int si, int sj) { return 4 * (fi * N - ((fi * (fi - 1)) >> 1) + (fj - fi)) + 2 * si + sj; };
+    for (int bi = 0; bi < nbt; ++bi)
+        for (int bj = 0; bj <= bi; ++bj)
+            for (int l = 0; l < 64; ++l)
+                for (int r = 0; r < 4; ++r) {
+                    const int I = 16 * bi + (l >> 4) + 4 * r, J = 16 * bj + (l & 15);
+                    int32_t dst = -1;
+                    if (I < P6 && J <= I) {
+                        const int fI = I / 6, iI = I % 6, fJ = J / 6, jJ = J % 6; // fJ <= fI
+                        // partial_entry(N, fI, iI, fJ, jJ) of ba_kernels.hip: off-diagonal blocks once (smaller frame = row of the task)
+                        const int el = fI == fJ ? 3 * (iI % 3) + (jJ % 3) : 3 * (jJ % 3) + (iI % 3);
+                        const int t = fI == fJ ? task_index(fI, fI, iI / 3, jJ / 3) : task_index(fJ, fI, jJ / 3, iI / 3);
+                        dst = (el << 24) | t;
+                    }
+                    table.push_back(dst);
+                }
+    return table;
+}
+
+// Large-window role (ba_lin_tp.h): chunks of <= 256 factors whose landmarks share ONE anchor frame (a chunk is cut where the anchor changes: the
+// reference's block order is anchor-sorted, any other order only makes more chunks), as many landmarks as the LDS holds U rows for; every chunk's
+// factors sorted by target frame (the direct part of J^T J is accumulated per target).  Needs dm.lm_mm and the other roles' grids.
+static void plan_large_window_chunks(const pvio_ba_problem *pb, int cus, int lm_wgs_cap, UploadPlan &pl) {
+    Dims &dm = pl.dm;
+    const int N = dm.N, M = dm.M, F = dm.F;
+    pl.tp_tile_dst = tp_tile_dst_table(N, dm.P6);
+    dm.lm_slots = tp_landmark_slots(dm, F > 0 ? (int)(((long long)kLinThreads * M + F - 1) / F) : 64);
+    pl.chunk_lm = cut_chunks(pb, dm.lm_slots, true);
+    const std::vector<int32_t> &chunk_lm = pl.chunk_lm;
+    dm.n_chunks = (int)chunk_lm.size() - 1;
+    // two workgroups per CU where their LDS allows (tp_landmark_slots) and the kernel is held to 256 registers (k_linearize<T <= 2, true>)
+    const int per_cu = (linearize_lds_bytes(dm) <= 80 * 1024 && tiles_per_thread(dm) <= 2) ? 2 : 1;
+    dm.G_lm = std::max(1, std::min(dm.n_chunks, lm_wgs_cap > 0 ? lm_wgs_cap : per_cu * cus - (dm.G_plane + dm.G_pre + dm.G_prior)));
+    if (dm.n_chunks > 0) { // contiguous chunk ranges (a range mostly shares one anchor frame): no more workgroups than ranges
+        const int per_wg = (dm.n_chunks + dm.G_lm - 1) / dm.G_lm;
+        dm.G_lm = std::max(1, (dm.n_chunks + per_wg - 1) / per_wg);
+    }
+    pl.chunk_geo.assign((size_t)dm.n_chunks * 8, 0);
+    pl.chunk_tptr.assign((size_t)dm.n_chunks * (N + 1), 0);
+    pl.chunk_perm.assign((size_t)std::max(F, 1), 0);
+    for (int c = 0; c < dm.n_chunks; ++c) {
+        const int o0 = pb->lm_obs_ptr[chunk_lm[c]], o1 = pb->lm_obs_ptr[chunk_lm[c + 1]];
+        int32_t *g = pl.chunk_geo.data() + (size_t)c * 8;
+        g[0] = chunk_lm[c], g[1] = chunk_lm[c + 1] - chunk_lm[c], g[2] = o0, g[3] = o1 - o0;
+        g[4] = pb->lm_anchor_frame[chunk_lm[c]];
+        int32_t *tp = pl.chunk_tptr.data() + (size_t)c * (N + 1);
+        for (int o = o0; o < o1; ++o) ++tp[pb->obs_frame[o] + 1];
+        for (int t = 0; t < N; ++t) tp[t + 1] += tp[t];
+        int fill[kMaxFrames] = {0};
+        for (int o = o0; o < o1; ++o) { // counting sort, stable: a target's factors in landmark order
+            const int t = pb->obs_frame[o];
+            pl.chunk_perm[(size_t)o0 + tp[t] + fill[t]++] = (uint8_t)(o - o0);
+        }
+    }
+}
+
+// plan: the validated problem + the solver's configuration -> what the kernels are configured by.  No HIP call, no member written.
+void BASolver::plan_upload(const pvio_ba_problem *pb, UploadPlan &pl) const {
+    const UploadSwitches &sw = upload_switches();
+    const int N = pb->n_frames, M = pb->n_landmarks, F = pb->n_obs, cus = cus_;
+    Dims &dm = pl.dm;
+    dm.N = N, dm.M = M, dm.F = F;
+    dm.use_inertial = pb->use_inertial ? 1 : 0;
+    dm.prior_n = pb->prior_n;
+    dm.d = (dm.use_inertial || dm.prior_n > 0) ? 15 : 6;
+    dm.P = dm.d * N, dm.P6 = 6 * N;
+    dm.n_tasks = 4 * N * (N + 1) / 2;
+    dm.max_iter = pb->max_iterations;
+    dm.world = world_, dm.rank = rank_;
+    dm.n_plane = pb->n_plane_factors;
+    dm.n_rot = pb->n_rot_priors;
+
+    // ---- block usage (Ceres removes constant and unreferenced parameter blocks from the reduced program) ----
+    std::vector<uint8_t> pose_used(N, 0), motion_used(N, 0);
+    pl.pre_valid.assign(N, 0);
+    pl.obs_lm.assign(F, 0);
+    uint32_t seen_any = 0; // bit f: frame f is some landmark's target
+    for (int l = 0; l < M; ++l) {
+        const int b = pb->lm_obs_ptr[l], e = pb->lm_obs_ptr[l + 1];
+        if (e > b) pose_used[pb->lm_anchor_frame[l]] = 1;
+        std::fill(pl.obs_lm.begin() + b, pl.obs_lm.begin() + e, l);
+        seen_any |= pl.lm_seen[(size_t)l];
+    }
+    for (int f = 0; f < N; ++f)
+        if ((seen_any >> f) & 1u) pose_used[f] = 1;
+    if (dm.use_inertial)
+        for (int j = 1; j < N; ++j)
+            if (pb->preint_valid[j]) {
+                pl.pre_valid[j] = 1;
+                pose_used[j - 1] = pose_used[j] = motion_used[j - 1] = motion_used[j] = 1;
+            }
+    pl.prior_slot.assign(N, -1); // frame -> slot of the prior (the last one that names it, like the kernels' old search)
+    for (int i = 0; i < dm.prior_n; ++i) {
+        const int f = pb->prior_frames[i];
+        pose_used[f] = motion_used[f] = 1;
+        pl.prior_slot[f] = i;
+    }
+    pl.rot_slot.assign(N, -1); // rotation priors: at most one per frame; one on a fixed frame is a constant block and is dropped
+    for (int i = 0; i < dm.n_rot; ++i) {
+        pl.rot_slot[pb->rot_prior_frame[i]] = i;
+        pose_used[pb->rot_prior_frame[i]] = 1;
+    }
+    for (int f = 0; f < dm.n_plane; ++f) {
+        bool any_free = false;
+        for (int o = pb->plane_obs_ptr[f]; o < pb->plane_obs_ptr[f + 1]; ++o) any_free |= !pb->frame_fixed[pb->plane_obs_frame[o]];
+        if (any_free)
+            for (int o = pb->plane_obs_ptr[f]; o < pb->plane_obs_ptr[f + 1]; ++o) pose_used[pb->plane_obs_frame[o]] = 1;
+    }
+    pl.pose_active.assign(N, 0), pl.motion_active.assign(N, 0);
+    for (int i = 0; i < N; ++i) {
+        pl.pose_active[i] = pose_used[i] && !pb->frame_fixed[i];
+        pl.motion_active[i] = (dm.d == 15) && motion_used[i];
+    }
+    if (pb->lm_multiplicity && std::any_of(pb->lm_multiplicity, pb->lm_multiplicity + M, [](int32_t m) { return m != 1; }))
+        pl.lm_mult.assign(pb->lm_multiplicity, pb->lm_multiplicity + M);
+
+    // ---- the roles of k_linearize: plane chunks, one workgroup per IMU factor and per prior frame, landmark chunks ----
+    dm.plane_slots = (int)std::max<size_t>(1, std::min<size_t>(kLinLdsBudget / 8 / (dm.P6 + 2), (size_t)kLinThreads));
+    for (int f = 0; f <= dm.n_plane; f += dm.plane_slots) pl.plane_chunk.push_back(f);
+    if (pl.plane_chunk.back() != dm.n_plane) pl.plane_chunk.push_back(dm.n_plane);
+    dm.n_plane_chunks = (int)pl.plane_chunk.size() - 1;
+    dm.G_plane = dm.n_plane > 0 ? std::max(1, std::min(dm.n_plane_chunks, std::max(1, cus / 4))) : 0;
+    dm.G_pre = dm.use_inertial ? N - 1 : 0;
+    dm.G_prior = dm.prior_n; // one workgroup per prior frame
+    // Large windows take the throughput role (ba_lin_tp.h: chunks of 256 factors walked by workgroups that keep their accumulators, Schur complement on the
+    // matrix cores); its prologue + flush + first chunk cost ~30 us whatever the window, the register-tile role's time grows with the landmarks per workgroup:
+    // same-box A/B over 6 .. 24 frames (profiles/r6_lin_mode_ab.txt): they cross at ~40 000 factors (10 x 5000: 35.7 -> 32.4 us, 10 x 10 000: 66.7 -> 40.2 us,
+    // 16 x 3000: 48.4 -> 41.0 us; 10 x 3000: 28.1 against 31.3 us, 6 x 3000: 24.5 against 34.5 us)
+    // (a window without landmarks has no chunks: the register-tile role's empty walk handles it)
+    dm.lm_mm = ((lin_mode_ == 2 && M > 0) || (lin_mode_ == 0 && F >= 40000)) ? 1 : 0;
+    const int lm_wgs_cap = sw.lm_wgs >= 1 ? std::min(sw.lm_wgs, 4 * cus) : 0;
+    if (dm.lm_mm) plan_large_window_chunks(pb, cus, lm_wgs_cap, pl);
+    else plan_register_tile_chunks(pb, cus, lm_wgs_cap, pl);
+    // pvio_hip_opts::reuse_identical_candidates.  Not on landmark shards: their k_reduce feeds an all-reduce that sums IN PLACE, a skipped slot
+    // would add the last slot's sums to themselves.
+    dm.reuse_cand = (reuse_cand_ && !sharded_) ? 1 : 0;
+
+    // ---- back-substitution: 16 landmarks per workgroup pass (16 lanes each); <= 64 partial rows (one per lane of the wave that sums them) until a
+    // large window needs the whole chip ----
+    dm.G_back = M <= 4096 ? std::max(1, std::min(64, (M + 15) / 16)) : std::min(cus, (M + 63) / 64);
+    dm.fuse_backsub = (!sharded_ && M <= sw.fuse_max && !sw.fuse_off) ? 1 : 0; // beyond one landmark per thread the separate launch is faster
+    dm.n_back_rows = (sharded_ || dm.fuse_backsub) ? 1 : dm.G_back;
+    for (int fi = 0; fi < N; ++fi) // 3x3 tile tasks over the upper block triangle
+        for (int fj = fi; fj < N; ++fj)
+            for (int s = 0; s < 4; ++s) pl.task_desc.push_back(fi | (fj << 8) | ((s >> 1) << 16) | ((s & 1) << 17));
+
+    // ---- k_dense.  Tile image: k_reduce also assembles the reduced system entry by entry where the dense kernel's tile owners load it from (single
+    // GPU, system resident in LDS/registers; landmark-sharded runs build it from the all-reduced `red`: k_reduce phase 2) ----
+    int lds_matrix = 0;
+    dense_lds_bytes(dm, &lds_matrix);
+    dm.use_img = 1;
+    dm.img_sz = (int)dense_tile_doubles(dm);
+    // split finalize: with a separate k_backsub launch on one GPU, k_dense leaves the gradient max-norm, the state / trace copies and
+    // (register-resident factorization: the image is what it factors) the pose part of v^T H v to that launch.
+    // (landmark shards: every rank runs the same finalize workgroup on the same all-reduced data; the pose part of v^T H v is formed by
+    // rank 0's k_backsub alone -- the exchange step behind it sums the ranks' rows)
+    dm.split_fin = (!dm.fuse_backsub && !sw.split_off) ? 1 : 0;
+    dm.qvv_back = (dm.split_fin && lds_matrix) ? 1 : 0;
+    // look-ahead form of the register-resident factorization
+    dm.dense_la = (lds_matrix && (sw.dense_la < 0 ? kDenseLookAheadDefault : sw.dense_la != 0)) ? 1 : 0;
+    // the image in the form the accumulators hold once the scaling exists
+    dm.img_scaled = (dm.dense_la && dm.split_fin && dm.qvv_back && !sw.img_scaled_off) ? 1 : 0;
+}
+
+// What allocate and stage hand to commit.
+struct UploadWork {
+    View v{};
+    const double *fs_init = nullptr, *rho_init = nullptr; // initial state inside the inputs slab
+    bool grew = false;          // a pool slot was allocated or moved: the captured graph holds stale addresses
+    bool sent_directly = false; // an array went from where it lay, asynchronously: the stream must drain before upload() returns
+};
+
+template <typename T>
+static bool dev(DevicePool &pool, const char *name, size_t n, T **dst, bool *grew) {
+    T *p = static_cast<T *>(pool.get(name, n * sizeof(T), grew));
+    *dst = p;
+    return p != nullptr;
+}
+
+// allocate: state and work buffers of a window of w.v.dm's shape, zeroed where the kernels expect it.
+int BASolver::allocate(UploadWork &w) {
+    View &v = w.v;
+    const Dims &dm = v.dm;
+    bool *grew = &w.grew, ok = true;
+    const size_t Ns = dm.N, Ms = std::max(dm.M, 1), Fs = std::max(dm.F, 1), Dp = 15 * (size_t)dm.prior_n, P = dm.P;
+    double *Lambda = nullptr, *eta = nullptr, *ST = nullptr; // written by k_prior_prep (stage), read-only from then on
+    ok &= dev(pool_, "prior_Lambda", Dp * Dp, &Lambda, grew);
+    ok &= dev(pool_, "prior_eta", Dp, &eta, grew);
+    ok &= dev(pool_, "prior_ST", Dp * Dp, &ST, grew);
+    v.prior_Lambda = Lambda, v.prior_eta = eta, v.prior_ST = ST;
+    ok &= dev(pool_, "ctrl", 1, &v.ctrl, grew);
+    ok &= dev(pool_, "cand_rec", 24, &v.cand_rec, grew);
+    ok &= dev(pool_, "fs", 2 * Ns * 16, &v.fs, grew);
+    ok &= dev(pool_, "fs_user", Ns * 16, &v.fs_user, grew);
+    ok &= dev(pool_, "bias0_lin", Ns * 6, &v.bias0_lin, grew);
+    ok &= dev(pool_, "rho", 2 * Ms, &v.rho, grew);
+    ok &= dev(pool_, "cl", Ms, &v.cl, grew);
+    ok &= dev(pool_, "Hll", 2 * Ms, &v.Hll, grew);
+    ok &= dev(pool_, "bl", 2 * Ms, &v.bl, grew);
+    ok &= dev(pool_, "Dl", 2 * Ms, &v.Dl, grew);
+    ok &= dev(pool_, "ghl", 2 * Ms, &v.ghl, grew);
+    ok &= dev(pool_, "gnl", 2 * Ms, &v.gnl, grew);
+    ok &= dev(pool_, "Wa", 2 * Ms * 6, &v.Wa, grew);
+    ok &= dev(pool_, "Wt", 2 * Fs * 6, &v.Wt, grew);
+    const size_t G = (size_t)dm.G_lm + dm.G_plane, nS = (size_t)dm.n_tasks * 9, nV = (size_t)kNumPoseVec * dm.P6;
+    ok &= dev(pool_, "part_S", G * nS, &v.part_S, grew);
+    ok &= dev(pool_, "part_vec", G * nV, &v.part_vec, grew);
+    ok &= dev(pool_, "part_scal", G * kNumLinScal, &v.part_scal, grew);
+    ok &= dev(pool_, "red", nS + nV + kNumLinScal + (size_t)world_, &v.red, grew); // + one max slot per rank
+    ok &= dev(pool_, "back_part", (size_t)std::max(dm.G_back, 1) * kNumBackScal, &v.back_part, grew);
+    ok &= dev(pool_, "back_red", kNumBackScal, &v.back_red, grew);
+    ok &= dev(pool_, "pre_H", Ns * 900, &v.pre_H, grew);
+    ok &= dev(pool_, "pre_g", Ns * 30, &v.pre_g, grew);
+    ok &= dev(pool_, "pre_cost", Ns, &v.pre_cost, grew);
+    ok &= dev(pool_, "prior_H", Dp * Dp, &v.prior_H, grew);
+    ok &= dev(pool_, "prior_g", Dp, &v.prior_g, grew);
+    ok &= dev(pool_, "prior_cost", (size_t)std::max(dm.prior_n, 1), &v.prior_cost, grew);
+    {
+        // arrays the kernels read for every frame whether the window has the factor or not: the prior's gradient / diagonal by frame
+        // (k_dense's vector assembly; frames without a prior slot stay zero) and the rotation-prior blocks (k_reduce / k_dense; zero
+        // when the window has none).  One block, one memset.
+        double *zb = nullptr;
+        ok &= dev(pool_, "zero_block", Ns * 42 + 1, &zb, grew);
+        v.prior_gd = zb, v.rot_H = zb + Ns * 30, v.rot_g = v.rot_H + Ns * 9, v.rot_cost = v.rot_g + Ns * 3;
+        if (ok && check(hipMemsetAsync(zb, 0, (dm.n_rot == 0 ? Ns * 42 + 1 : Ns * 30) * sizeof(double), stream_), "memset zero block")) return PVIO_ERR_HIP;
+    }
+    ok &= dev(pool_, "Smat", dense_tile_doubles(dm), &v.Smat, grew);
+    // the tile image is zero wherever nothing is ever written (+ one tile of zeros behind it: what k_dense's waves load into the accumulator
+    // slots they do not own)
+    ok &= dev(pool_, "img", (size_t)dm.img_sz + 256, &v.img, grew);
+    if (ok && dm.use_img && check(hipMemsetAsync(v.img, 0, ((size_t)dm.img_sz + 256) * sizeof(double), stream_), "memset img")) return PVIO_ERR_HIP;
+    ok &= dev(pool_, "cp", P, &v.cp, grew);
+    ok &= dev(pool_, "cpl", P, &v.cpl, grew);
+    ok &= dev(pool_, "vraw", P, &v.vraw, grew);
+    ok &= dev(pool_, "Dp", P, &v.Dp, grew);
+    ok &= dev(pool_, "gtot", P, &v.gtot, grew);
+    ok &= dev(pool_, "ghp", P, &v.ghp, grew);
+    ok &= dev(pool_, "vstep", P, &v.vstep, grew);
+    ok &= dev(pool_, "ystep", P, &v.ystep, grew);
+    ok &= dev(pool_, "lm_quality", Ms, &v.lm_quality, grew);
+    ok &= dev(pool_, "lm_valid", Ms, &v.lm_valid, grew);
+    ok &= dev(pool_, "trace", (size_t)dm.max_iter + 2, &v.trace, grew);
+    if (!ok) return fail(PVIO_ERR_OUT_OF_MEMORY, "device allocation / upload failed");
+    return PVIO_OK;
+}
+
 // Host inputs of one upload: gathered in ONE pinned staging buffer and sent with ONE DMA into one device slab (a window is
 // ~35 small arrays; a pageable hipMemcpyAsync each cost more than the solve's first iterations).  Offsets are 256-byte
 // aligned; an array that is not given (null) keeps its place uninitialized, like the separate allocations it replaces.
@@ -103,461 +509,153 @@ struct StagedUpload {
         const size_t bytes = n * sizeof(T);
         items.push_back({(n && src) ? static_cast<const void *>(src) : nullptr, bytes, 0, reinterpret_cast<const void **>(dst)});
     }
+    template <typename T>
+    void add(const std::vector<T> &src, const T **dst) { add(src.data(), src.size(), dst); } // (an empty vector: no source)
 };
 
-template <typename T>
-static bool dev(DevicePool &pool, const char *name, size_t n, T **dst, bool *grew) {
-    T *p = static_cast<T *>(pool.get(name, n * sizeof(T), grew));
-    *dst = p;
-    return p != nullptr;
-}
-
-int BASolver::upload(const pvio_ba_problem *pb, const pvio_ba_state *st, bool may_return_early) {
-    if (!pb || !st || !st->frame_state) return fail(PVIO_ERR_INVALID_ARGUMENT, "null problem/state");
-    const int N = pb->n_frames, M = pb->n_landmarks, F = pb->n_obs;
-    if (N < 1 || N > kMaxFrames) return fail(PVIO_ERR_UNSUPPORTED, "n_frames must be in [1, 32]");
-    if (M < 0 || F < 0 || (M > 0 && !st->lm_inv_depth)) return fail(PVIO_ERR_INVALID_ARGUMENT, "bad landmark arrays");
-    if (!pb->frame_fixed || !pb->cam_extrinsic || !pb->imu_extrinsic || !pb->sqrt_inv_cov || !pb->intrinsics) return fail(PVIO_ERR_INVALID_ARGUMENT, "null per-frame array");
-    if (M > 0 && (!pb->lm_anchor_frame || !pb->lm_anchor_z || !pb->lm_obs_ptr)) return fail(PVIO_ERR_INVALID_ARGUMENT, "null landmark array");
-    if (F > 0 && (!pb->obs_frame || !pb->obs_z)) return fail(PVIO_ERR_INVALID_ARGUMENT, "null observation array");
-    if (M > 0 && (pb->lm_obs_ptr[0] != 0 || pb->lm_obs_ptr[M] != F)) return fail(PVIO_ERR_INVALID_ARGUMENT, "lm_obs_ptr must start at 0 and end at n_obs");
-    if (pb->prior_n < 0 || pb->prior_n > N || pb->max_iterations < 0 || pb->n_plane_factors < 0) return fail(PVIO_ERR_INVALID_ARGUMENT, "negative count / prior_n > n_frames");
-    if (pb->prior_n > 0 && (!pb->prior_frames || !pb->prior_S || !pb->prior_s || !pb->prior_lin_state)) return fail(PVIO_ERR_INVALID_ARGUMENT, "null prior array");
-    if (pb->use_inertial && (!pb->preint_valid || !pb->preint_delta || !pb->preint_sqrt_inv_cov || !pb->preint_jacobian)) return fail(PVIO_ERR_INVALID_ARGUMENT, "null pre-integration array");
-    if (pb->n_plane_factors > 0) {
-        if (!pb->plane_obs_ptr || !pb->plane_obs_frame || !pb->plane_obs_z || !pb->plane_normal || !pb->plane_distance) return fail(PVIO_ERR_INVALID_ARGUMENT, "null plane array");
-        if (pb->plane_obs_ptr[0] != 0) return fail(PVIO_ERR_INVALID_ARGUMENT, "plane_obs_ptr must start at 0");
-        for (int f = 0; f < pb->n_plane_factors; ++f) {
-            if (pb->plane_obs_ptr[f + 1] < pb->plane_obs_ptr[f]) return fail(PVIO_ERR_INVALID_ARGUMENT, "plane_obs_ptr is not a valid CSR");
-            for (int o = pb->plane_obs_ptr[f]; o < pb->plane_obs_ptr[f + 1]; ++o)
-                if (pb->plane_obs_frame[o] < 0 || pb->plane_obs_frame[o] >= N) return fail(PVIO_ERR_INVALID_ARGUMENT, "plane observation frame out of range");
-        }
-    }
-    if (check(hipSetDevice(device_), "hipSetDevice")) return PVIO_ERR_HIP;
-    Dims dm{};
-    dm.N = N, dm.M = M, dm.F = F;
-    dm.use_inertial = pb->use_inertial ? 1 : 0;
-    dm.prior_n = pb->prior_n;
-    dm.d = (dm.use_inertial || dm.prior_n > 0) ? 15 : 6;
-    dm.P = dm.d * N, dm.P6 = 6 * N;
-    dm.n_tasks = 4 * N * (N + 1) / 2;
-    dm.max_iter = pb->max_iterations;
-    max_solver_time_ = pb->max_solver_time > 0 ? pb->max_solver_time : 0.0;
-    dm.world = world_, dm.rank = rank_;
-    dm.n_plane = pb->n_plane_factors;
-
-    // ---- block usage (Ceres removes constant and unreferenced parameter blocks from the reduced program) ----
-    std::vector<uint8_t> pose_used(N, 0), motion_used(N, 0), pose_active(N, 0), motion_active(N, 0), pre_valid(N, 0);
-    std::vector<int32_t> obs_lm(F, 0);
-    std::vector<uint32_t> lm_seen((size_t)std::max(M, 1), 0u); // bit f: the landmark is observed in frame f
-    int maxK = 1;
-    for (int l = 0; l < M; ++l) {
-        const int b = pb->lm_obs_ptr[l], e = pb->lm_obs_ptr[l + 1];
-        if (b < 0 || e < b || e > F) return fail(PVIO_ERR_INVALID_ARGUMENT, "lm_obs_ptr is not a valid CSR");
-        const int a = pb->lm_anchor_frame[l];
-        if (a < 0 || a >= N) return fail(PVIO_ERR_INVALID_ARGUMENT, "anchor frame out of range");
-        if (e > b) pose_used[a] = 1;
-        maxK = std::max(maxK, e - b);
-        uint32_t seen = 0;
-        for (int o = b; o < e; ++o) {
-            const int t = pb->obs_frame[o];
-            if (t < 0 || t >= N || t == a) return fail(PVIO_ERR_INVALID_ARGUMENT, "observation frame out of range or equal to the anchor");
-            if (seen & (1u << t)) return fail(PVIO_ERR_UNSUPPORTED, "a landmark lists the same target frame twice");
-            seen |= 1u << t;
-            obs_lm[o] = l;
-            pose_used[t] = 1;
-        }
-        lm_seen[(size_t)l] = seen;
-    }
-    if (maxK > kLinThreads) return fail(PVIO_ERR_UNSUPPORTED, "too many observations per landmark");
-    if (dm.use_inertial && pb->preint_valid)
-        for (int j = 1; j < N; ++j)
-            if (pb->preint_valid[j]) {
-                pre_valid[j] = 1;
-                pose_used[j - 1] = pose_used[j] = motion_used[j - 1] = motion_used[j] = 1;
-            }
-    std::vector<int32_t> prior_slot(N, -1); // frame -> slot of the prior (the last one that names it, like the kernels' old search)
-    for (int i = 0; i < dm.prior_n; ++i) {
-        const int f = pb->prior_frames[i];
-        if (f < 0 || f >= N) return fail(PVIO_ERR_INVALID_ARGUMENT, "prior frame out of range");
-        pose_used[f] = motion_used[f] = 1;
-        prior_slot[f] = i;
-    }
-    // rotation priors: at most one per frame; one on a fixed frame is a constant block and is dropped
-    std::vector<int32_t> rot_slot(N, -1);
-    if (pb->n_rot_priors < 0 || (pb->n_rot_priors > 0 && (!pb->rot_prior_frame || !pb->rot_prior_q0 || !pb->rot_prior_sqrt_info)))
-        return fail(PVIO_ERR_INVALID_ARGUMENT, "bad rotation prior arrays");
-    for (int i = 0; i < pb->n_rot_priors; ++i) {
-        const int f = pb->rot_prior_frame[i];
-        if (f < 0 || f >= N) return fail(PVIO_ERR_INVALID_ARGUMENT, "rotation prior frame out of range");
-        if (rot_slot[f] >= 0) return fail(PVIO_ERR_UNSUPPORTED, "more than one rotation prior on a frame");
-        rot_slot[f] = i;
-        pose_used[f] = 1;
-    }
-    dm.n_rot = pb->n_rot_priors;
-    for (int f = 0; f < dm.n_plane; ++f) {
-        bool any_free = false;
-        for (int o = pb->plane_obs_ptr[f]; o < pb->plane_obs_ptr[f + 1]; ++o) any_free |= !pb->frame_fixed[pb->plane_obs_frame[o]];
-        if (any_free)
-            for (int o = pb->plane_obs_ptr[f]; o < pb->plane_obs_ptr[f + 1]; ++o) pose_used[pb->plane_obs_frame[o]] = 1;
-    }
-    for (int i = 0; i < N; ++i) {
-        pose_active[i] = pose_used[i] && !pb->frame_fixed[i];
-        motion_active[i] = (dm.d == 15) && motion_used[i];
-    }
-
-    if (cus_ <= 0) { // asked once: the query is slow
-        hipDeviceProp_t prop;
-        if (check(hipGetDeviceProperties(&prop, device_), "hipGetDeviceProperties")) return PVIO_ERR_HIP;
-        cus_ = std::max(1, prop.multiProcessorCount);
-    }
-    const int cus = cus_;
-    // ---- landmark chunks: <= lm_slots landmarks and <= 256 factors each (one thread per factor).  A small window is
-    // latency-bound per workgroup, so chunks are sized to put one chunk on every CU (256 on MI355X) rather than to fill
-    // the LDS; a large window falls back to LDS-filling chunks that each workgroup walks in a grid-stride loop. ----
-    const size_t lds_budget = 112 * 1024;
-    dm.plane_slots = (int)std::max<size_t>(1, std::min<size_t>(lds_budget / 8 / (dm.P6 + 2), (size_t)kLinThreads));
-    std::vector<int32_t> plane_chunk;
-    for (int f = 0; f <= dm.n_plane; f += dm.plane_slots) plane_chunk.push_back(f);
-    if (plane_chunk.empty() || plane_chunk.back() != dm.n_plane) plane_chunk.push_back(dm.n_plane);
-    dm.n_plane_chunks = (int)plane_chunk.size() - 1;
-    dm.G_plane = dm.n_plane > 0 ? std::max(1, std::min(dm.n_plane_chunks, std::max(1, cus / 4))) : 0;
-    dm.G_pre = dm.use_inertial ? N - 1 : 0;
-    dm.G_prior = dm.prior_n; // one workgroup per prior frame
-    // One workgroup fits on a CU (registers, LDS) and the IMU / prior workgroups are the longest: the landmark chunks get
-    // the CUs that are left, so that the whole grid is resident at once instead of queueing a second round behind it.
-    // One landmark chunk per free CU.  Round 5 measured the alternative the 22x traffic of the partial rows suggests -- fewer, fatter workgroups, i.e.
-    // fewer rows for k_reduce to sum (PVIO_HIP_LM_WGS=n caps the count; profiles/r5_ab_partials.txt): the traffic falls with the count and the
-    // iteration rate with it, because a workgroup's chain grows with the landmarks it holds (the per-landmark sums and the tile accumulation walk
-    // them one after another): 48 rows = 12 161 against 14 112 iterations/s, k_linearize 18.4 -> 29.2 us for 0.4 us less in k_reduce.
-    // (an experiment switch, unsupported: read once per process, clamped to [1, 4 x CUs] -- the partial-row buffers are sized from the resulting grid below,
-    // so any value in the range is safe; anything else is ignored)
-    static const int lm_wgs_env = std::getenv("PVIO_HIP_LM_WGS") ? std::atoi(std::getenv("PVIO_HIP_LM_WGS")) : 0;
-    const int lm_wgs_cap = lm_wgs_env >= 1 ? std::min(lm_wgs_env, 4 * cus) : 0;
-    int lm_cus = std::max(1, cus - dm.G_plane - dm.G_pre - dm.G_prior);
-    if (lm_wgs_cap > 0) lm_cus = lm_wgs_cap; // (may exceed the free CUs: more than one workgroup per CU where registers and LDS allow)
-    const int slots_lds = (int)std::max<size_t>(1, std::min<size_t>(lds_budget / 8 / (40 * N + 46), (size_t)kLinThreads));
-    const int slots_spread = std::max(1, (M + lm_cus - 1) / lm_cus);
-    dm.lm_slots = std::min(slots_lds, slots_spread);
-    std::vector<int32_t> chunk_lm;
-    chunk_lm.push_back(0);
-    {
-        int cnt = 0, fac = 0;
-        for (int l = 0; l < M; ++l) {
-            const int k = pb->lm_obs_ptr[l + 1] - pb->lm_obs_ptr[l];
-            if (cnt > 0 && (cnt + 1 > dm.lm_slots || fac + k > kLinThreads)) {
-                chunk_lm.push_back(l);
-                cnt = 0, fac = 0;
-            }
-            ++cnt, fac += k;
-        }
-        if (M > 0) chunk_lm.push_back(M);
-    }
-    dm.n_chunks = (int)chunk_lm.size() - 1;
-    dm.G_lm = std::max(1, std::min(dm.n_chunks, lm_cus));
-    // Large windows take the throughput role (ba_lin_tp.h: chunks of 256 factors walked by workgroups that keep their accumulators, Schur complement on the
-    // matrix cores); its prologue + flush + first chunk cost ~30 us whatever the window, the register-tile role's time grows with the landmarks per workgroup:
-    // same-box A/B over 6 .. 24 frames (profiles/r6_lin_mode_ab.txt): they cross at ~40 000 factors (10 x 5000: 35.7 -> 32.4 us, 10 x 10 000: 66.7 -> 40.2 us,
-    // 16 x 3000: 48.4 -> 41.0 us; 10 x 3000: 28.1 against 31.3 us, 6 x 3000: 24.5 against 34.5 us)
-    dm.lm_mm = (lin_mode_ == 2 && M > 0) || (lin_mode_ == 0 && F >= 40000); // (a window without landmarks has no chunks: the register-tile role's empty walk handles it)
-    // Large windows (ba_lin_tp.h): chunks of <= 256 factors whose landmarks share ONE anchor frame (a chunk is cut where the anchor changes: the
-    // reference's block order is anchor-sorted, any other order only makes more chunks), as many landmarks as the LDS holds U rows for; every
-    // chunk's factors sorted by target frame (the direct part of J^T J is accumulated per target)
-    std::vector<int32_t> chunk_tptr, chunk_geo, tp_tile_dst;
-    std::vector<uint8_t> chunk_perm;
-    if (dm.lm_mm) {
-        // scatter table of the Schur tiles' accumulator entries into the element-major 3 x 3-task partial row (the flush of ba_lin_tp.h): entry r of
-        // lane l of tile (bi, bj) is element (16 bi + (l >> 4) + 4 r, 16 bj + (l & 15)) of the lower triangle
-        const int nbt = tp_u_stride(dm.P6) >> 4;
-        auto task_index = [&](int fi, int fj, int si, int sj) { return 4 * (fi * N - ((fi * (fi - 1)) >> 1) + (fj - fi)) + 2 * si + sj; };
-        for (int bi = 0; bi < nbt; ++bi)
-            for (int bj = 0; bj <= bi; ++bj)
-                for (int l = 0; l < 64; ++l)
-                    for (int r = 0; r < 4; ++r) {
-                        const int I = 16 * bi + (l >> 4) + 4 * r, J = 16 * bj + (l & 15);
-                        int32_t dst = -1;
-                        if (I < dm.P6 && J <= I) {
-                            const int fI = I / 6, iI = I % 6, fJ = J / 6, jJ = J % 6; // fJ <= fI
-                            // partial_entry(N, fI, iI, fJ, jJ) of ba_kernels.hip: off-diagonal blocks once (smaller frame = row of the task)
-                            const int el = fI == fJ ? 3 * (iI % 3) + (jJ % 3) : 3 * (jJ % 3) + (iI % 3);
-                            const int t = fI == fJ ? task_index(fI, fI, iI / 3, jJ / 3) : task_index(fJ, fI, jJ / 3, iI / 3);
-                            dst = (el << 24) | t;
-                        }
-                        tp_tile_dst.push_back(dst);
-                    }
-    }
-    if (dm.lm_mm) {
-        dm.lm_slots = tp_landmark_slots(dm, F > 0 ? (int)(((long long)kLinThreads * M + F - 1) / F) : 64);
-        chunk_lm.assign(1, 0);
-        int cnt = 0, fac = 0, anchor = -1;
-        for (int l = 0; l < M; ++l) {
-            const int k = pb->lm_obs_ptr[l + 1] - pb->lm_obs_ptr[l];
-            if (cnt > 0 && (cnt + 1 > dm.lm_slots || fac + k > kLinThreads || pb->lm_anchor_frame[l] != anchor)) {
-                chunk_lm.push_back(l);
-                cnt = 0, fac = 0;
-            }
-            anchor = pb->lm_anchor_frame[l];
-            ++cnt, fac += k;
-        }
-        if (M > 0) chunk_lm.push_back(M);
-        dm.n_chunks = (int)chunk_lm.size() - 1;
-        // two workgroups per CU where their LDS allows (tp_landmark_slots) and the kernel is held to 256 registers (k_linearize<T <= 2, true>)
-        dm.lm_mm = 1;
-        const int per_cu = (linearize_lds_bytes(dm) <= 80 * 1024 && tiles_per_thread(dm) <= 2) ? 2 : 1;
-        dm.G_lm = std::max(1, std::min(dm.n_chunks, lm_wgs_cap > 0 ? lm_wgs_cap : per_cu * cus - (dm.G_plane + dm.G_pre + dm.G_prior)));
-        chunk_geo.assign((size_t)dm.n_chunks * 8, 0);
-        for (int c = 0; c < dm.n_chunks; ++c) {
-            int32_t *g = chunk_geo.data() + (size_t)c * 8;
-            g[0] = chunk_lm[c], g[1] = chunk_lm[c + 1] - chunk_lm[c], g[2] = pb->lm_obs_ptr[chunk_lm[c]], g[3] = pb->lm_obs_ptr[chunk_lm[c + 1]] - g[2];
-            g[4] = pb->lm_anchor_frame[chunk_lm[c]];
-        }
-        chunk_tptr.assign((size_t)dm.n_chunks * (N + 1), 0);
-        chunk_perm.assign((size_t)std::max(F, 1), 0);
-        for (int c = 0; c < dm.n_chunks; ++c) {
-            const int o0 = pb->lm_obs_ptr[chunk_lm[c]], o1 = pb->lm_obs_ptr[chunk_lm[c + 1]];
-            int32_t *tp = chunk_tptr.data() + (size_t)c * (N + 1);
-            for (int o = o0; o < o1; ++o) ++tp[pb->obs_frame[o] + 1];
-            for (int t = 0; t < N; ++t) tp[t + 1] += tp[t];
-            int fill[kMaxFrames] = {0};
-            for (int o = o0; o < o1; ++o) { // counting sort, stable: a target's factors in landmark order
-                const int t = pb->obs_frame[o];
-                chunk_perm[(size_t)o0 + tp[t] + fill[t]++] = (uint8_t)(o - o0);
-            }
-        }
-    }
-    // pvio_hip_opts::reuse_identical_candidates.  Not on landmark shards: their k_reduce feeds an all-reduce that sums IN PLACE, a skipped slot
-    // would add the last slot's sums to themselves.
-    dm.reuse_cand = (reuse_cand_ && !sharded_) ? 1 : 0;
-    if (dm.lm_mm && dm.n_chunks > 0) { // contiguous chunk ranges (a range mostly shares one anchor frame): no more workgroups than ranges
-        const int per_wg = (dm.n_chunks + dm.G_lm - 1) / dm.G_lm;
-        dm.G_lm = std::max(1, (dm.n_chunks + per_wg - 1) / per_wg);
-    }
-    // 16 landmarks per workgroup pass (16 lanes each); <= 64 partial rows (one per lane of the wave that sums them) until a
-    // large window needs the whole chip
-    dm.G_back = M <= 4096 ? std::max(1, std::min(64, (M + 15) / 16)) : std::min(cus, (M + 63) / 64);
-    // (PVIO_HIP_FUSE_BACKSUB=0: tests -- small windows through the separate k_backsub launch, i.e. the split-finalize form)
-    static const bool fuse_off = std::getenv("PVIO_HIP_FUSE_BACKSUB") != nullptr && std::atoi(std::getenv("PVIO_HIP_FUSE_BACKSUB")) == 0;
-    // (PVIO_HIP_FUSE_BACKSUB_MAX: experiments -- the landmark count up to which the back-substitution stays inside k_dense; clamped to 16 .. 4096)
-    static const int fuse_max = std::getenv("PVIO_HIP_FUSE_BACKSUB_MAX") ? std::min(4096, std::max(16, std::atoi(std::getenv("PVIO_HIP_FUSE_BACKSUB_MAX")))) : 256;
-    dm.fuse_backsub = (!sharded_ && M <= fuse_max && !fuse_off) ? 1 : 0; // beyond one landmark per thread the separate launch is faster
-    dm.n_back_rows = (sharded_ || dm.fuse_backsub) ? 1 : dm.G_back;
-
-    // 3x3 tile tasks over the upper block triangle
-    std::vector<int32_t> task_desc;
-    for (int fi = 0; fi < N; ++fi)
-        for (int fj = fi; fj < N; ++fj)
-            for (int s = 0; s < 4; ++s) task_desc.push_back(fi | (fj << 8) | ((s >> 1) << 16) | ((s & 1) << 17));
-
-    // ---- device buffers ----
-    bool grew = false, sent_directly = false;
-    View v{};
-    v.dm = dm;
-    const size_t Ns = N, Ms = std::max(M, 1), Fs = std::max(F, 1);
-    bool ok = true;
+// stage: the caller's arrays, the plan's and the initial state -> the inputs slab, queued on the stream; then the prior's derived forms.
+// The items point into `pl`, `pb`, `st` and h_init_*: all of them stay where they are until the stream has drained.
+int BASolver::stage_inputs(const pvio_ba_problem *pb, const pvio_ba_state *st, const UploadPlan &pl, UploadWork &w) {
+    View &v = w.v;
+    const Dims &dm = v.dm;
+    const size_t Ns = dm.N, M = dm.M, F = dm.F, Dp = 15 * (size_t)dm.prior_n;
     StagedUpload stage;
     stage.add(pb->frame_fixed, Ns, &v.frame_fixed);
-    stage.add(pose_active.data(), Ns, &v.pose_active);
-    stage.add(motion_active.data(), Ns, &v.motion_active);
+    stage.add(pl.pose_active, &v.pose_active);
+    stage.add(pl.motion_active, &v.motion_active);
     stage.add(pb->cam_extrinsic, Ns * 7, &v.cam_ext);
     stage.add(pb->imu_extrinsic, Ns * 7, &v.imu_ext);
     stage.add(pb->sqrt_inv_cov, Ns * 4, &v.sic);
     stage.add(pb->intrinsics, Ns * 4, &v.intr);
-    stage.add(pb->lm_anchor_frame, (size_t)M, &v.lm_anchor);
-    stage.add(pb->lm_obs_ptr, (size_t)M + 1, &v.lm_ptr);
-    stage.add(pb->lm_anchor_z, (size_t)M * 2, &v.lm_zref);
-    std::vector<double> lm_mult; // duplicate residual blocks (bundle_adjustor.cpp:165-179); staged only when some landmark counts twice
-    if (pb->lm_multiplicity) {
-        bool any = false;
-        for (int l = 0; l < M; ++l) {
-            if (pb->lm_multiplicity[l] < 1) return fail(PVIO_ERR_INVALID_ARGUMENT, "lm_multiplicity must be >= 1");
-            any |= pb->lm_multiplicity[l] != 1;
-        }
-        if (any) {
-            lm_mult.resize((size_t)M);
-            for (int l = 0; l < M; ++l) lm_mult[(size_t)l] = (double)pb->lm_multiplicity[l];
-        }
-    }
-    stage.add(lm_mult.empty() ? (const double *)nullptr : lm_mult.data(), lm_mult.size(), &v.lm_mult);
-    stage.add(pb->obs_frame, (size_t)F, &v.obs_frame);
-    stage.add(pb->obs_z, (size_t)F * 2, &v.obs_z);
-    stage.add(obs_lm.data(), (size_t)F, &v.obs_lm);
-    stage.add(lm_seen.data(), (size_t)M, &v.lm_seen);
-    stage.add(chunk_lm.data(), chunk_lm.size(), &v.chunk_lm);
-    stage.add(chunk_tptr.empty() ? (const int32_t *)nullptr : chunk_tptr.data(), chunk_tptr.size(), &v.chunk_tptr);
-    stage.add(chunk_geo.empty() ? (const int32_t *)nullptr : chunk_geo.data(), chunk_geo.size(), &v.chunk_geo);
-    stage.add(chunk_perm.empty() ? (const uint8_t *)nullptr : chunk_perm.data(), chunk_perm.size(), &v.chunk_perm);
-    stage.add(tp_tile_dst.empty() ? (const int32_t *)nullptr : tp_tile_dst.data(), tp_tile_dst.size(), &v.tp_tile_dst);
-    stage.add(task_desc.data(), task_desc.size(), &v.task_desc);
-    stage.add(pre_valid.data(), Ns, &v.pre_valid);
+    stage.add(pb->lm_anchor_frame, M, &v.lm_anchor);
+    stage.add(pb->lm_obs_ptr, M + 1, &v.lm_ptr);
+    stage.add(pb->lm_anchor_z, M * 2, &v.lm_zref);
+    stage.add(pl.lm_mult, &v.lm_mult);
+    stage.add(pb->obs_frame, F, &v.obs_frame);
+    stage.add(pb->obs_z, F * 2, &v.obs_z);
+    stage.add(pl.obs_lm, &v.obs_lm);
+    stage.add(pl.lm_seen.data(), M, &v.lm_seen);
+    stage.add(pl.chunk_lm, &v.chunk_lm);
+    stage.add(pl.chunk_tptr, &v.chunk_tptr);
+    stage.add(pl.chunk_geo, &v.chunk_geo);
+    stage.add(pl.chunk_perm, &v.chunk_perm);
+    stage.add(pl.tp_tile_dst, &v.tp_tile_dst);
+    stage.add(pl.task_desc, &v.task_desc);
+    stage.add(pl.pre_valid, &v.pre_valid);
     stage.add(dm.use_inertial ? pb->preint_delta : nullptr, Ns * 11, &v.pre_delta);
     stage.add(dm.use_inertial ? pb->preint_sqrt_inv_cov : nullptr, Ns * 225, &v.pre_U);
     stage.add(dm.use_inertial ? pb->preint_jacobian : nullptr, Ns * 45, &v.pre_jac);
-    const size_t Dp = 15 * (size_t)dm.prior_n;
     stage.add(pb->prior_frames, (size_t)dm.prior_n, &v.prior_frames);
     stage.add(pb->prior_S, Dp * Dp, &v.prior_S);
     stage.add(pb->prior_s, Dp, &v.prior_s);
     stage.add(pb->prior_lin_state, (size_t)dm.prior_n * 16, &v.prior_lin);
-    double *Lambda = nullptr, *eta = nullptr, *ST = nullptr;
-    ok &= dev(pool_, "prior_Lambda", Dp * Dp, &Lambda, &grew);
-    ok &= dev(pool_, "prior_eta", Dp, &eta, &grew);
-    ok &= dev(pool_, "prior_ST", Dp * Dp, &ST, &grew);
-    v.prior_Lambda = Lambda, v.prior_eta = eta, v.prior_ST = ST;
     const size_t npo = dm.n_plane ? (size_t)pb->plane_obs_ptr[dm.n_plane] : 0;
     stage.add(pb->plane_obs_ptr, (size_t)dm.n_plane + 1, &v.plane_ptr);
     stage.add(pb->plane_obs_frame, npo, &v.plane_frame);
-    stage.add(plane_chunk.data(), plane_chunk.size(), &v.plane_chunk);
+    stage.add(pl.plane_chunk, &v.plane_chunk);
     stage.add(pb->plane_obs_z, npo * 2, &v.plane_z);
     stage.add(pb->plane_normal, (size_t)dm.n_plane * 3, &v.plane_normal);
     stage.add(pb->plane_distance, (size_t)dm.n_plane, &v.plane_dist);
     v.plane_sic = pb->plane_sqrt_inv_cov;
-    stage.add(rot_slot.data(), Ns, &v.rot_slot);
-    stage.add(prior_slot.data(), Ns, &v.prior_slot);
+    stage.add(pl.rot_slot, &v.rot_slot);
+    stage.add(pl.prior_slot, &v.prior_slot);
     stage.add(pb->rot_prior_q0, (size_t)dm.n_rot * 4, &v.rot_q0);
     stage.add(pb->rot_prior_sqrt_info, (size_t)dm.n_rot * 9, &v.rot_W);
-    // state + work
-    ok &= dev(pool_, "ctrl", 1, &v.ctrl, &grew);
-    ok &= dev(pool_, "cand_rec", 24, &v.cand_rec, &grew);
-    ok &= dev(pool_, "fs", 2 * Ns * 16, &v.fs, &grew);
-    ok &= dev(pool_, "fs_user", Ns * 16, &v.fs_user, &grew);
-    ok &= dev(pool_, "bias0_lin", Ns * 6, &v.bias0_lin, &grew);
-    ok &= dev(pool_, "rho", 2 * Ms, &v.rho, &grew);
-    ok &= dev(pool_, "cl", Ms, &v.cl, &grew);
-    ok &= dev(pool_, "Hll", 2 * Ms, &v.Hll, &grew);
-    ok &= dev(pool_, "bl", 2 * Ms, &v.bl, &grew);
-    ok &= dev(pool_, "Dl", 2 * Ms, &v.Dl, &grew);
-    ok &= dev(pool_, "ghl", 2 * Ms, &v.ghl, &grew);
-    ok &= dev(pool_, "gnl", 2 * Ms, &v.gnl, &grew);
-    ok &= dev(pool_, "Wa", 2 * Ms * 6, &v.Wa, &grew);
-    ok &= dev(pool_, "Wt", 2 * Fs * 6, &v.Wt, &grew);
-    const size_t G = (size_t)dm.G_lm + dm.G_plane, nS = (size_t)dm.n_tasks * 9, nV = (size_t)kNumPoseVec * dm.P6;
-    ok &= dev(pool_, "part_S", G * nS, &v.part_S, &grew);
-    ok &= dev(pool_, "part_vec", G * nV, &v.part_vec, &grew);
-    ok &= dev(pool_, "part_scal", G * kNumLinScal, &v.part_scal, &grew);
-    ok &= dev(pool_, "red", nS + nV + kNumLinScal + (size_t)world_, &v.red, &grew); // + one max slot per rank
-    ok &= dev(pool_, "back_part", (size_t)std::max(dm.G_back, 1) * kNumBackScal, &v.back_part, &grew);
-    ok &= dev(pool_, "back_red", kNumBackScal, &v.back_red, &grew);
-    ok &= dev(pool_, "pre_H", Ns * 900, &v.pre_H, &grew);
-    ok &= dev(pool_, "pre_g", Ns * 30, &v.pre_g, &grew);
-    ok &= dev(pool_, "pre_cost", Ns, &v.pre_cost, &grew);
-    ok &= dev(pool_, "prior_H", Dp * Dp, &v.prior_H, &grew);
-    ok &= dev(pool_, "prior_g", Dp, &v.prior_g, &grew);
-    ok &= dev(pool_, "prior_cost", (size_t)std::max(dm.prior_n, 1), &v.prior_cost, &grew);
-    {
-        // arrays the kernels read for every frame whether the window has the factor or not: the prior's gradient / diagonal by frame
-        // (k_dense's vector assembly; frames without a prior slot stay zero) and the rotation-prior blocks (k_reduce / k_dense; zero
-        // when the window has none).  One block, one memset.
-        double *zb = nullptr;
-        ok &= dev(pool_, "zero_block", Ns * 42 + 1, &zb, &grew);
-        v.prior_gd = zb, v.rot_H = zb + Ns * 30, v.rot_g = v.rot_H + Ns * 9, v.rot_cost = v.rot_g + Ns * 3;
-        if (ok && check(hipMemsetAsync(zb, 0, (dm.n_rot == 0 ? Ns * 42 + 1 : Ns * 30) * sizeof(double), stream_), "memset zero block")) return PVIO_ERR_HIP;
-    }
-    const size_t P = dm.P;
-    ok &= dev(pool_, "Smat", dense_tile_doubles(dm), &v.Smat, &grew);
-    // tile image: k_reduce also assembles the reduced system entry by entry where the dense kernel's tile owners load it
-    // from (single GPU, system resident in LDS/registers); zero wherever nothing is ever written
-    {
-        int lds_matrix = 0;
-        dense_lds_bytes(dm, &lds_matrix);
-        const size_t img_sz = dense_tile_doubles(dm);
-        v.dm.use_img = 1; // (landmark-sharded runs build it from the all-reduced `red`: k_reduce phase 2)
-        v.dm.img_sz = (int)img_sz;
-        dm.use_img = v.dm.use_img, dm.img_sz = v.dm.img_sz;
-        // split finalize: with a separate k_backsub launch on one GPU, k_dense leaves the gradient max-norm, the state / trace copies
-        // and (register-resident factorization: the image is what it factors) the pose part of v^T H v to that launch.
-        // PVIO_HIP_SPLIT_FIN=0 keeps everything in k_dense (A/B timing, tests of both forms).
-        static const bool split_off = std::getenv("PVIO_HIP_SPLIT_FIN") != nullptr && std::atoi(std::getenv("PVIO_HIP_SPLIT_FIN")) == 0;
-        // (landmark shards: every rank runs the same finalize workgroup on the same all-reduced data; the pose part of v^T H v is formed by
-        // rank 0's k_backsub alone -- the exchange step behind it sums the ranks' rows)
-        dm.split_fin = (!dm.fuse_backsub && !split_off) ? 1 : 0;
-        dm.qvv_back = (dm.split_fin && dm.use_img && lds_matrix) ? 1 : 0;
-        v.dm.split_fin = dm.split_fin, v.dm.qvv_back = dm.qvv_back;
-        // look-ahead form of the register-resident factorization (PVIO_HIP_DENSE_LA=0 / 1 overrides the default)
-        static const int la_env = std::getenv("PVIO_HIP_DENSE_LA") ? std::atoi(std::getenv("PVIO_HIP_DENSE_LA")) : -1;
-        dm.dense_la = (lds_matrix && dm.use_img && (la_env < 0 ? kDenseLookAheadDefault : la_env != 0)) ? 1 : 0;
-        v.dm.dense_la = dm.dense_la;
-        // the image in the form the accumulators hold once the scaling exists (PVIO_HIP_IMG_SCALED=0: k_dense scales every time)
-        static const bool img_scaled_off = std::getenv("PVIO_HIP_IMG_SCALED") != nullptr && std::atoi(std::getenv("PVIO_HIP_IMG_SCALED")) == 0;
-        dm.img_scaled = (dm.dense_la && dm.split_fin && dm.qvv_back && !img_scaled_off) ? 1 : 0;
-        v.dm.img_scaled = dm.img_scaled;
-        // (+ one tile of zeros behind the image: what k_dense's waves load into the accumulator slots they do not own)
-        ok &= dev(pool_, "img", img_sz + 256, &v.img, &grew);
-        if (ok && v.dm.use_img && check(hipMemsetAsync(v.img, 0, (img_sz + 256) * sizeof(double), stream_), "memset img")) return PVIO_ERR_HIP;
-    }
-    ok &= dev(pool_, "cp", P, &v.cp, &grew);
-    ok &= dev(pool_, "cpl", P, &v.cpl, &grew);
-    ok &= dev(pool_, "vraw", P, &v.vraw, &grew);
-    ok &= dev(pool_, "Dp", P, &v.Dp, &grew);
-    ok &= dev(pool_, "gtot", P, &v.gtot, &grew);
-    ok &= dev(pool_, "ghp", P, &v.ghp, &grew);
-    ok &= dev(pool_, "vstep", P, &v.vstep, &grew);
-    ok &= dev(pool_, "ystep", P, &v.ystep, &grew);
-    ok &= dev(pool_, "lm_quality", Ms, &v.lm_quality, &grew);
-    ok &= dev(pool_, "lm_valid", Ms, &v.lm_valid, &grew);
-    trace_cap_ = dm.max_iter + 2;
-    ok &= dev(pool_, "trace", (size_t)trace_cap_, &v.trace, &grew);
-    v.trace_states = nullptr;
-    if (!ok) return fail(PVIO_ERR_OUT_OF_MEMORY, "device allocation / upload failed");
-
     // initial state: kept on the host (tiny for frames) and on the device in buffer 0
     h_init_fs_.assign(st->frame_state, st->frame_state + Ns * 16);
     h_init_rho_.assign(st->lm_inv_depth, st->lm_inv_depth + M);
-    stage.add(h_init_fs_.data(), Ns * 16, &fs_init_);
-    stage.add(h_init_rho_.data(), (size_t)M, &rho_init_);
-    // ---- one staging pass, one DMA ----
-    {
-        // small arrays ride in the staging buffer (front of the slab); a big one (the observation arrays of a 50 000-landmark
-        // window) is cheaper sent from where it lies than copied twice, and lives behind them
-        constexpr size_t kDirect = 1 << 20;
-        size_t staged = 0, total = 0;
-        for (auto &it : stage.items)
-            if (it.bytes < kDirect) it.off = staged, staged += (std::max<size_t>(it.bytes, 8) + 255) & ~(size_t)255;
-        total = staged;
-        for (auto &it : stage.items)
-            if (it.bytes >= kDirect) it.off = total, total += (it.bytes + 255) & ~(size_t)255;
-        char *slab = static_cast<char *>(pool_.get("inputs", total, &grew));
-        if (!slab) return fail(PVIO_ERR_OUT_OF_MEMORY, "device allocation failed");
-        if (stage_in_flight_) {
-            // the last upload returned with its staged copy queued and the call that was to synchronize behind it ended early (an error in
-            // solve() / marginalize() before their own synchronization): drain the stream before the staging buffer is written again
-            if (check(hipStreamSynchronize(stream_), "staging buffer still in flight")) return PVIO_ERR_HIP;
-            stage_in_flight_ = false;
-        }
-        if (staged > h_stage_cap_) {
-            if (h_stage_) (void)hipHostFree(h_stage_);
-            h_stage_ = nullptr, h_stage_cap_ = 0;
-            const size_t cap = staged + staged / 2; // (pinned host memory is the expensive allocation: headroom for the next windows of the sequence)
-            if (hipHostMalloc(&h_stage_, cap) != hipSuccess) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
-            h_stage_cap_ = cap;
-        }
-        for (const auto &it : stage.items) {
-            if (it.src && it.bytes < kDirect) std::memcpy(static_cast<char *>(h_stage_) + it.off, it.src, it.bytes);
-            *it.dst = slab + it.off;
-        }
-        if (check(hipMemcpyAsync(slab, h_stage_, staged, hipMemcpyHostToDevice, stream_), "H2D inputs")) return PVIO_ERR_HIP;
-        for (const auto &it : stage.items)
-            if (it.src && it.bytes >= kDirect) {
-                if (check(hipMemcpyAsync(slab + it.off, it.src, it.bytes, hipMemcpyHostToDevice, stream_), "H2D inputs")) return PVIO_ERR_HIP;
-                sent_directly = true;
-            }
-    }
-    if (lm_mult.empty()) v.lm_mult = nullptr; // no duplicates: the kernels take the unscaled path
-    if (dm.prior_n > 0 && check(launch_prior_prep(v.prior_S, v.prior_s, (int)Dp, Lambda, eta, ST, stream_), "k_prior_prep")) return PVIO_ERR_HIP;
+    stage.add(h_init_fs_, &w.fs_init);
+    stage.add(h_init_rho_, &w.rho_init);
 
-    const bool dims_changed = std::memcmp(&v.dm, &v_.dm, sizeof(Dims)) != 0;
-    if (grew || dims_changed || std::memcmp(&v, &v_, sizeof(View)) != 0) invalidate_graph();
-    v_ = v;
+    // ---- one staging pass, one DMA ----
+    // small arrays ride in the staging buffer (front of the slab); a big one (the observation arrays of a 50 000-landmark
+    // window) is cheaper sent from where it lies than copied twice, and lives behind them
+    constexpr size_t kDirect = 1 << 20;
+    size_t staged = 0, total = 0;
+    for (auto &it : stage.items)
+        if (it.bytes < kDirect) it.off = staged, staged += (std::max<size_t>(it.bytes, 8) + 255) & ~(size_t)255;
+    total = staged;
+    for (auto &it : stage.items)
+        if (it.bytes >= kDirect) it.off = total, total += (it.bytes + 255) & ~(size_t)255;
+    char *slab = static_cast<char *>(pool_.get("inputs", total, &w.grew));
+    if (!slab) return fail(PVIO_ERR_OUT_OF_MEMORY, "device allocation failed");
+    if (stage_in_flight_) {
+        // the last upload returned with its staged copy queued and the call that was to synchronize behind it ended early (an error in
+        // solve() / marginalize() before their own synchronization): drain the stream before the staging buffer is written again
+        if (check(hipStreamSynchronize(stream_), "staging buffer still in flight")) return PVIO_ERR_HIP;
+        stage_in_flight_ = false;
+    }
+    if (staged > h_stage_cap_) {
+        if (h_stage_) (void)hipHostFree(h_stage_);
+        h_stage_ = nullptr, h_stage_cap_ = 0;
+        const size_t cap = staged + staged / 2; // (pinned host memory is the expensive allocation: headroom for the next windows of the sequence)
+        if (hipHostMalloc(&h_stage_, cap) != hipSuccess) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+        h_stage_cap_ = cap;
+    }
+    for (const auto &it : stage.items) {
+        if (it.src && it.bytes < kDirect) std::memcpy(static_cast<char *>(h_stage_) + it.off, it.src, it.bytes);
+        *it.dst = slab + it.off;
+    }
+    if (check(hipMemcpyAsync(slab, h_stage_, staged, hipMemcpyHostToDevice, stream_), "H2D inputs")) return PVIO_ERR_HIP;
+    for (const auto &it : stage.items)
+        if (it.src && it.bytes >= kDirect) {
+            if (check(hipMemcpyAsync(slab + it.off, it.src, it.bytes, hipMemcpyHostToDevice, stream_), "H2D inputs")) return PVIO_ERR_HIP;
+            w.sent_directly = true;
+        }
+    if (pl.lm_mult.empty()) v.lm_mult = nullptr; // no duplicates: the kernels take the unscaled path
+    if (dm.prior_n > 0 && check(launch_prior_prep(v.prior_S, v.prior_s, (int)Dp, const_cast<double *>(v.prior_Lambda), const_cast<double *>(v.prior_eta),
+                                                  const_cast<double *>(v.prior_ST), stream_), "k_prior_prep"))
+        return PVIO_ERR_HIP;
+    return PVIO_OK;
+}
+
+// commit: the new window becomes the context's.  The only step that writes members other than the staging buffers.
+int BASolver::commit(const pvio_ba_problem *pb, const UploadWork &w, bool may_return_early) {
+    const bool dims_changed = std::memcmp(&w.v.dm, &v_.dm, sizeof(Dims)) != 0;
+    if (w.grew || dims_changed || std::memcmp(&w.v, &v_, sizeof(View)) != 0) invalidate_graph();
+    v_ = w.v;
+    fs_init_ = w.fs_init, rho_init_ = w.rho_init;
     uploaded_ = true;
     solves_since_upload_ = 0;
-    // The caller of the public entry point may release its arrays as soon as this returns, and arrays that went straight from where they
-    // lay (>= 1 MB; some of them temporaries of this function) must have left: wait.  A solve that follows immediately on the same stream
+    trace_cap_ = w.v.dm.max_iter + 2;
+    max_solver_time_ = pb->max_solver_time > 0 ? pb->max_solver_time : 0.0;
+    // The caller of the public entry point may release its arrays as soon as upload() returns, and arrays that went straight from where they
+    // lay (>= 1 MB; some of them the plan's, which upload() destroys) must have left: wait.  A solve that follows immediately on the same stream
     // (pvio_hip_ba_solve: may_return_early) synchronizes anyway before ITS caller gets the arrays back; the staged part was copied into the
-    // pinned buffer above, which is not written again before the next upload.
-    if (may_return_early && !sent_directly) {
+    // pinned buffer, which is not written again before the next upload.
+    if (may_return_early && !w.sent_directly) {
         stage_in_flight_ = true; // the DMA may still be reading h_stage_: the next upload waits for it before it writes there
         return PVIO_OK;
     }
     stage_in_flight_ = false;
     return check(hipStreamSynchronize(stream_), "upload sync");
+}
+
+int BASolver::upload(const pvio_ba_problem *pb, const pvio_ba_state *st, bool may_return_early) {
+    UploadPlan plan; // outlives commit's wait for the arrays that are sent from where they lie
+    const Reject bad = validate_upload(pb, st, plan.lm_seen);
+    if (bad.code != PVIO_OK) return fail(bad.code, bad.msg); // the previous window stays as it was
+    if (check(hipSetDevice(device_), "hipSetDevice")) return PVIO_ERR_HIP;
+    if (cus_ <= 0) { // asked once: the query is slow
+        hipDeviceProp_t prop;
+        if (check(hipGetDeviceProperties(&prop, device_), "hipGetDeviceProperties")) return PVIO_ERR_HIP;
+        cus_ = std::max(1, prop.multiProcessorCount);
+    }
+    plan_upload(pb, plan);
+    UploadWork work;
+    work.v.dm = plan.dm;
+    int rc = allocate(work);
+    if (rc == PVIO_OK) rc = stage_inputs(pb, st, plan, work);
+    if (rc != PVIO_OK) {
+        // Between windows: a pool slot that grew has freed what v_ and the captured graph point to, and the slab is half written.  Neither may be
+        // used again (solve() / download() answer "no problem uploaded"), and nothing may still be reading the plan's or the caller's arrays.
+        uploaded_ = false;
+        invalidate_graph();
+        (void)hipStreamSynchronize(stream_);
+        stage_in_flight_ = false;
+        return rc;
+    }
+    return commit(pb, work, may_return_early);
 }
 
 int BASolver::enqueue_slot(hipEvent_t *ev) {
@@ -942,24 +1040,13 @@ static bool lu_inverse15(const double *Ain, double *inv) { // Eigen's .inverse()
 // false (nothing written) when the landmark arrays are not a window upload() accepts: the caller then passes the whole window on, to be rejected.
 static bool marg_subset(const pvio_ba_problem *pb, const pvio_ba_state *st, int victim, std::vector<int32_t> &anchor, std::vector<double> &anchor_z,
                         std::vector<int32_t> &ptr, std::vector<int32_t> &frame, std::vector<double> &z, std::vector<int32_t> &mult, std::vector<double> &rho) {
-    const int N = pb->n_frames, M = pb->n_landmarks, F = pb->n_obs;
-    if (N < 1 || N > kMaxFrames || M < 0 || F < 0) return false;
-    if (M > 0 && (!st->lm_inv_depth || !pb->lm_anchor_frame || !pb->lm_anchor_z || !pb->lm_obs_ptr)) return false;
-    if (F > 0 && (!pb->obs_frame || !pb->obs_z)) return false;
-    if (M == 0 || pb->lm_obs_ptr[0] != 0 || pb->lm_obs_ptr[M] != F) return false;
-    std::vector<uint8_t> keep((size_t)M, 0);
+    const int M = pb->n_landmarks;
+    std::vector<uint32_t> keep; // check_landmarks: the frames that observe the landmark; from here on: whether the victim is one of them (or its anchor)
+    if (check_landmarks(pb, st, keep).code != PVIO_OK || M == 0) return false;
     size_t n_keep = 0, f_keep = 0;
     for (int l = 0; l < M; ++l) {
-        const int b = pb->lm_obs_ptr[l], e = pb->lm_obs_ptr[l + 1], a = pb->lm_anchor_frame[l];
-        if (b < 0 || e < b || e > F || a < 0 || a >= N) return false;
-        if (pb->lm_multiplicity && pb->lm_multiplicity[l] < 1) return false;
-        uint32_t seen = 0;
-        for (int o = b; o < e; ++o) {
-            const int t = pb->obs_frame[o];
-            if (t < 0 || t >= N || t == a || (seen & (1u << t))) return false;
-            seen |= 1u << t;
-        }
-        if (a == victim || ((seen >> victim) & 1u)) keep[(size_t)l] = 1, ++n_keep, f_keep += (size_t)(e - b);
+        keep[(size_t)l] = pb->lm_anchor_frame[l] == victim || ((keep[(size_t)l] >> victim) & 1u);
+        if (keep[(size_t)l]) ++n_keep, f_keep += (size_t)(pb->lm_obs_ptr[l + 1] - pb->lm_obs_ptr[l]);
     }
     anchor.clear(), anchor_z.clear(), frame.clear(), z.clear(), mult.clear(), rho.clear();
     // (+ 1: a victim without landmarks still hands upload() arrays, not null pointers)

@@ -33,6 +33,9 @@ class DevicePool { // grow-only device allocations keyed by name
     size_t total_ = 0;
 };
 
+struct UploadPlan; // what an upload derives on the host
+struct UploadWork; // the View an upload is building
+
 class BASolver {
   public:
     BASolver(int device, int rank, int world, bool use_graph);
@@ -60,6 +63,11 @@ class BASolver {
     int run_slots(int n_slots);
     int enqueue_slot(hipEvent_t *ev = nullptr);
     void invalidate_graph();
+    // the steps of upload() behind its argument checks (ba_solver.cpp)
+    void plan_upload(const pvio_ba_problem *pb, UploadPlan &plan) const;
+    int allocate(UploadWork &w);
+    int stage_inputs(const pvio_ba_problem *pb, const pvio_ba_state *st, const UploadPlan &plan, UploadWork &w);
+    int commit(const pvio_ba_problem *pb, const UploadWork &w, bool may_return_early);
 
     int device_, rank_, world_;
     bool sharded_; // world_ > 1, or forced for tests: eager launches + all-reduces + assembly from the reduced buffer

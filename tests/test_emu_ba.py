@@ -1,7 +1,9 @@
 """Kernel-logic check WITHOUT a GPU: the product sources (pvio_amd/csrc) compiled against the fiber emulator
 (tests/hipemu, test infrastructure only) must reproduce the oracle iteration by iteration.  The real parity
 tests are tests/test_gpu_ba.py (-m gpu, same checks through libpvio_hip.so)."""
+import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -80,44 +82,103 @@ def test_emulated_resident_solve_is_repeatable(emu_ctx, oracle):
     assert (outs[0][0] == outs[1][0]).all() and (outs[0][1] == outs[1][1]).all() and outs[0][2] == outs[1][2]
 
 
+INVALID, UNSUPPORTED = -1, -5  # PVIO_ERR_INVALID_ARGUMENT, PVIO_ERR_UNSUPPORTED (include/pvio_hip.h)
+
+
+def _null_anchor_z(c):
+    c.lm_anchor_z = C.cast(None, capi.c_double_p)
+
+
+def _set(name, index, value):
+    def edit(q):
+        a = getattr(q, name).copy()
+        a[index] = value(q) if callable(value) else value
+        setattr(q, name, a)
+    return edit
+
+
+def _two_rot_priors(q):
+    q.rot_prior_frame = np.array([1, 1], np.int32)
+    q.rot_prior_q0 = np.tile([0, 0, 0, 1.0], (2, 1))
+    q.rot_prior_sqrt_info = np.tile(np.eye(3).ravel(), (2, 1))
+
+
+# name -> (window, edit of the BAProblem, edit of the pvio_ba_problem or None, status, a distinguishing part of the message)
+BROKEN_WINDOWS = {
+    "same_target_twice": ("vision_small", lambda q: q.obs_frame.__setitem__(1, q.obs_frame[0]), None, UNSUPPORTED, "same target frame twice"),
+    "observation_in_the_anchor": ("vision_small", _set("obs_frame", 0, lambda q: q.lm_anchor_frame[0]), None, INVALID, "equal to the anchor"),
+    "lm_ptr_starts_below_0": ("plane", _set("lm_obs_ptr", 0, -1), None, INVALID, "lm_obs_ptr must start at 0"),
+    "lm_ptr_not_monotone": ("plane", _set("lm_obs_ptr", 2, lambda q: q.lm_obs_ptr[1] - 1), None, INVALID, "lm_obs_ptr is not a valid CSR"),
+    "plane_observation_outside": ("plane", _set("plane_obs_frame", 3, lambda q: q.n_frames), None, INVALID, "plane observation frame out of range"),
+    "negative_iterations": ("plane", lambda q: setattr(q, "max_iterations", -3), None, INVALID, "negative count"),
+    "two_rotation_priors_on_a_frame": ("plane", _two_rot_priors, None, UNSUPPORTED, "more than one rotation prior"),
+    "null_landmark_array": ("vision_small", lambda q: None, _null_anchor_z, INVALID, "null landmark array"),
+    "multiplicity_0": ("vision_duplicate_blocks", _set("lm_multiplicity", 3, 0), None, INVALID, "lm_multiplicity must be >= 1"),
+    "prior_frame_outside": ("vio_small", _set("prior_frames", 0, lambda q: q.n_frames), None, INVALID, "prior frame out of range"),
+}
+
+
+def _broken(oracle, name):
+    case, edit, edit_c, status, word = BROKEN_WINDOWS[name]
+    q = ba_compare.make(oracle, **ba_compare.CASES[case])
+    edit(q)
+    return q, edit_c, r"status %d \(.*%s" % (status, re.escape(word))
+
+
+def _upload_c(ctx, q, st, edit_c):
+    """HipContext.upload with the C struct edited on the way (what no numpy array can say: a null pointer)"""
+    pb, stc = q.as_c(), st.as_c()
+    if edit_c:
+        edit_c(pb)
+    ctx._check(ctx.lib.pvio_hip_ba_upload(ctx.ctx, C.byref(pb), C.byref(stc)), "pvio_hip_ba_upload")
+
+
 def test_rejects_bad_input(emu_ctx, oracle):
+    """PVIO_ERR_INVALID_ARGUMENT / UNSUPPORTED with the message of the first failing check, never an out-of-bounds read"""
+    from pvio_amd import BAState
     from pvio_amd.solver import HipError
-    pb = ba_compare.make(oracle, **ba_compare.CASES["vision_small"])
-    pb.obs_frame[1] = pb.obs_frame[0]  # same target frame twice for one landmark
-    with pytest.raises(HipError):
-        emu_ctx.solve(pb)
-    # CSR that does not start at 0 / is not monotone, plane observation outside the window, negative counts, a second
-    # rotation prior on one frame: PVIO_ERR_INVALID_ARGUMENT / UNSUPPORTED, never an out-of-bounds read
-    def broken(edit, **kw):
-        q = ba_compare.make(oracle, **dict(ba_compare.CASES["plane"], **kw))
-        edit(q)
-        with pytest.raises(HipError):
-            emu_ctx.solve(q)
+    for name in sorted(BROKEN_WINDOWS):
+        q, edit_c, expect = _broken(oracle, name)
+        with pytest.raises(HipError, match=expect):
+            _upload_c(emu_ctx, q, BAState(q), edit_c)
+        if edit_c is None:
+            with pytest.raises(HipError, match=expect):
+                emu_ctx.solve(q)
 
-    def shift_ptr(q):
-        q.lm_obs_ptr = q.lm_obs_ptr.copy()
-        q.lm_obs_ptr[0] = -1
-    broken(shift_ptr)
 
-    def dip(q):
-        q.lm_obs_ptr = q.lm_obs_ptr.copy()
-        q.lm_obs_ptr[2] = q.lm_obs_ptr[1] - 1
-    broken(dip)
+def test_rejected_upload_leaves_the_uploaded_window_usable(emu_ctx, oracle):
+    from pvio_amd import BAState, BASummary
+    from pvio_amd.solver import HipError
+    pb = ba_compare.make(oracle, **ba_compare.CASES["vio_small"])
+    emu_ctx.upload(pb)
+    outs = []
+    for k in range(2):
+        if k == 1:  # rejected by the last check there is (the multiplicities), with another time limit: nothing of it may stay
+            q, _, expect = _broken(oracle, "multiplicity_0")
+            q.max_solver_time = 1.0e-9
+            with pytest.raises(HipError, match=expect):
+                emu_ctx.upload(q)
+        sm = BASummary(pb)
+        emu_ctx.solve_resident(sm)
+        st = BAState(pb)
+        emu_ctx.download(st)
+        outs.append((st.frame_state.copy(), st.lm_inv_depth.copy(), sm.num_iterations))
+    assert outs[0][2] > 1
+    assert (outs[0][0] == outs[1][0]).all() and (outs[0][1] == outs[1][1]).all() and outs[0][2] == outs[1][2]
 
-    def plane_oob(q):
-        q.plane_obs_frame = q.plane_obs_frame.copy()
-        q.plane_obs_frame[3] = q.n_frames
-    broken(plane_oob)
 
-    def neg_iter(q):
-        q.max_iterations = -3
-    broken(neg_iter)
-
-    def two_rot(q):
-        q.rot_prior_frame = np.array([1, 1], np.int32)
-        q.rot_prior_q0 = np.tile([0, 0, 0, 1.0], (2, 1))
-        q.rot_prior_sqrt_info = np.tile(np.eye(3).ravel(), (2, 1))
-    broken(two_rot)
+@pytest.mark.parametrize("name", ["same_target_twice", "observation_in_the_anchor", "lm_ptr_not_monotone", "multiplicity_0"])
+def test_marginalize_rejects_what_upload_rejects(emu_ctx, oracle, name):
+    """a window whose landmark arrays are invalid is not cut down to the victim's landmarks: upload's own code and message"""
+    from pvio_amd import BAState
+    from pvio_amd.solver import HipError
+    q, _, expect = _broken(oracle, name)
+    st = BAState(q)
+    with pytest.raises(HipError, match=expect) as up:
+        emu_ctx.upload(q, st)
+    with pytest.raises(HipError, match=expect) as mg:
+        emu_ctx.marginalize(q, st, 1)
+    assert str(up.value).split("status")[1] == str(mg.value).split("status")[1]
 
 
 import marg_compare  # noqa: E402
