@@ -110,8 +110,11 @@ def check_adapter_post_passes(lib, oracle, **kw):
     return moved, exp["membership"].sum(0)[M:] == 0
 
 
-def check_adapter(lib, oracle, **kw):
+def check_adapter(lib, oracle, rewrite=None, **kw):
+    """rewrite: the window is passed through it first (tests/window_variants.py)"""
     pb = ba_compare.make(oracle, **kw)
+    if rewrite is not None:
+        pb = rewrite(pb)
     st0, sm0 = BAState(pb), BASummary(pb)
     oracle.solve(pb, st0, sm0)
     st1 = BAState(pb)

@@ -26,6 +26,17 @@ def test_adapter_solve_emulated(emu_host, oracle, name):
     host_compare.check_adapter(emu_host, oracle, **CASES[name])
 
 
+def _per_frame(oracle):
+    """every frame with its own camera extrinsic, sqrt_inv_cov, intrinsics and IMU extrinsic (tests/window_variants.py): the adapter reads all four
+    from the Frame objects, tests/host/roundtrip.cpp puts them there frame by frame"""
+    import window_variants
+    return lambda pb: window_variants.per_frame_calibration(pb, oracle, window_variants.FIELDS, seed=11)
+
+
+def test_adapter_solve_per_frame_calibration_emulated(emu_host, oracle):
+    print(host_compare.check_adapter(emu_host, oracle, rewrite=_per_frame(oracle), **CASES["vio"]))
+
+
 def test_adapter_marginalize_emulated(emu_host, oracle):
     host_compare.check_adapter_marginalize(emu_host, oracle, 0, n_frames=5, n_landmarks=50, use_inertial=True, visibility=4)
     host_compare.check_adapter_marginalize(emu_host, oracle, 2, n_frames=5, n_landmarks=50, use_inertial=True, visibility=4)
@@ -61,6 +72,12 @@ def test_adapter_solve_gpu(oracle, name):
     kw["n_landmarks"] *= 5
     kw["n_frames"] = 8
     print(name, host_compare.check_adapter(lib, oracle, **kw))
+
+
+@pytest.mark.gpu
+def test_adapter_solve_per_frame_calibration_gpu(oracle):
+    lib = host_compare.load("libpvio_host.so")
+    print(host_compare.check_adapter(lib, oracle, rewrite=_per_frame(oracle), **CASES["vio"]))
 
 
 @pytest.mark.gpu

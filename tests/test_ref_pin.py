@@ -271,10 +271,18 @@ def _window(kind, oracle):
         # tracks of planes with fewer than 20 members get their reprojection blocks a second (third) time: bundle_adjustor.cpp:165-179.
         # On the reference side these ARE small planes in the Map (ref_py.tracks_of_problem); the flat problem carries lm_multiplicity.
         return synth.make_window(n_frames=6, n_landmarks=90, use_inertial=True, visibility=4, seed=706, preintegrate=oracle.preintegrate, duplicate_fraction=0.35)
+    # windows make_window never produces (tests/window_variants.py): the oracle's handling of per-frame values and of the other gauge was
+    # pinned factor by factor only
+    if kind == "vio_per_frame":  # its own camera extrinsic, sqrt_inv_cov, intrinsics and IMU extrinsic in every frame
+        import window_variants
+        return window_variants.per_frame_calibration(_window("vio", oracle), oracle, window_variants.FIELDS, seed=707)
+    if kind == "vio_moved":  # world yaw of 2.9 rad (quaternions through w < 0), 1 km away, every second stored quaternion negated
+        import window_variants
+        return window_variants.move_gauge(_window("vio", oracle), 2.9, 1.0e3 * np.array([0.6, -0.64, 0.48]), True)[0]
     raise KeyError(kind)
 
 
-@pytest.mark.parametrize("kind", ["vision", "vio", "vio_zero_bias", "vio_plane", "plane", "vio_small_planes"])
+@pytest.mark.parametrize("kind", ["vision", "vio", "vio_zero_bias", "vio_plane", "plane", "vio_small_planes", "vio_per_frame", "vio_moved"])
 def test_solve_equals_reference(ref, oracle, kind):
     """The reference's BundleAdjustorSolver::solve (its own problem construction, cost functions, callbacks and post-solve pass,
     mini-Ceres underneath) against oracle_ba_solve: same accept / reject trace, states after every iteration, final states,
@@ -312,7 +320,8 @@ def test_solve_equals_reference(ref, oracle, kind):
 
 # plane kinds: the reference's own marginalize_frame skips TF_PLANE tracks; small planes are duplicate blocks of VALID tracks, listed once (:455-510)
 @pytest.mark.parametrize("kind,victim", [("vio", 0), ("vio", 2), ("vio", 5), ("vio_zero_bias", 0),
-                                         ("plane", 0), ("plane", 2), ("vio_plane", 0), ("vio_plane", 3), ("vio_small_planes", 0), ("vio_small_planes", 3)])
+                                         ("plane", 0), ("plane", 2), ("vio_plane", 0), ("vio_plane", 3), ("vio_small_planes", 0), ("vio_small_planes", 3),
+                                         ("vio_per_frame", 0), ("vio_per_frame", 3), ("vio_moved", 0), ("vio_moved", 3)])
 def test_marginalize_equals_reference(ref, oracle, kind, victim):
     """marginalize_frame -- bundle_adjustor.cpp:348-599: the information matrix / vector S^T S, S^T s of the new prior (eigenvector
     signs cancel) and the reprojection error pass (:321-336), after a solve"""
