@@ -111,11 +111,19 @@ def check_against_oracle_within_spread(ctx, oracle, pb, c=4.0):
     return dict(r, spread=sp["state"], tol=tol)
 
 
-def check_against_oracle(ctx, oracle, pb, state_tol=STATE_TOL, cost_rtol=1e-7, trace_scale=1.0, quality_atol=1e-5):
+def check_against_oracle(ctx, oracle, pb, state_tol=STATE_TOL, cost_rtol=1e-7, trace_scale=1.0, quality_atol=1e-5, cost_atol_rel=0.0):
+    """cost_atol_rel (default 0: costs are compared relatively, to cost_rtol) adds an absolute term cost_atol_rel * initial_cost to the cost
+    comparisons of the trace and of the final cost.  A solve that converges on noise-free data ends 10 to 14 orders of magnitude below the
+    cost it started from: what is left is the rounding residue of sums whose terms were of the size of the initial cost, and two correct
+    evaluations of it in different summation orders agree to ~1e-16 of THAT, not to 1e-7 of the residue (seen: every decision equal, every
+    state within 1e-10, final costs 3.7e-15 apart = 1.3e-7 of the residue).  The tests of such windows pass cost_atol_rel = cost_rtol: the
+    same 1e-7, at the scale of the solve.  Everything else -- termination, iteration and step counts, trace length, accept / reject flags,
+    mu, the states -- is compared as without it."""
     st0, sm0 = BAState(pb), BASummary(pb)
     oracle.solve(pb, st0, sm0)
     st1, sm1 = ctx.solve(pb)
     t0, t1 = sm0.trace(), sm1.trace()
+    cost_atol = cost_atol_rel * sm0.initial_cost
     assert sm1.termination == sm0.termination
     assert sm1.num_iterations == sm0.num_iterations
     assert sm1.num_successful_steps == sm0.num_successful_steps
@@ -124,7 +132,7 @@ def check_against_oracle(ctx, oracle, pb, state_tol=STATE_TOL, cost_rtol=1e-7, t
         assert a["iteration"] == b["iteration"]
         assert a["step_is_valid"] == b["step_is_valid"], (a, b)
         assert a["step_is_successful"] == b["step_is_successful"], (a, b)
-        np.testing.assert_allclose(b["cost"], a["cost"], rtol=cost_rtol)
+        np.testing.assert_allclose(b["cost"], a["cost"], rtol=cost_rtol, atol=cost_atol)
         ts = trace_scale  # (1 unless the caller widened the state tolerance to the oracle's own spread)
         np.testing.assert_allclose(b["trust_region_radius"], a["trust_region_radius"], rtol=1e-6 * ts)
         np.testing.assert_allclose(b["mu"], a["mu"], rtol=1e-12)
@@ -136,7 +144,7 @@ def check_against_oracle(ctx, oracle, pb, state_tol=STATE_TOL, cost_rtol=1e-7, t
     np.testing.assert_allclose(st1.frame_state, st0.frame_state, rtol=0, atol=state_tol)
     np.testing.assert_allclose(st1.lm_inv_depth, st0.lm_inv_depth, rtol=0, atol=state_tol)
     np.testing.assert_allclose(sm1.initial_cost, sm0.initial_cost, rtol=1e-8)
-    np.testing.assert_allclose(sm1.final_cost, sm0.final_cost, rtol=cost_rtol)
+    np.testing.assert_allclose(sm1.final_cost, sm0.final_cost, rtol=cost_rtol, atol=cost_atol)
     assert (st1.lm_valid == st0.lm_valid).all()
     np.testing.assert_allclose(st1.lm_quality, st0.lm_quality, rtol=0, atol=quality_atol)
     worst = max(np.abs(sm1.trace_states[k] - sm0.trace_states[k]).max() for k in range(len(t0)))

@@ -136,13 +136,33 @@ class DenseProblem:
         return np.concatenate(parts)
 
 
-def solve(pb, O, state_update=True):
-    """Returns (trace list of dicts, final frame_state, final rho, termination)."""
-    return solve_dense(DenseProblem(pb, O), pb.frame_state.copy(), pb.lm_inv_depth.copy(), pb.max_iterations, state_update)
+# which of solve_dense's six termination tests ended the solve (SolveResult.reason)
+LIMIT, GRADIENT, MIN_RADIUS, INVALID_STEPS, PARAMETER, FUNCTION = "limit", "gradient", "min_radius", "invalid_steps", "parameter", "function"
 
 
-def solve_dense(D, fs, rho, max_iterations, state_update=True):
-    """The loop itself, for any problem object with evaluate(fs, rho, user, jac) / plus / ambient / ncols."""
+class SolveResult(tuple):
+    """(trace, frame_state, rho, termination, iterations) -- unpacks as the plain 5-tuple it used to be -- plus
+      reason     which termination test fired (one of the six names above)
+      deciding   (value, threshold) of the quantity that test compared: the gradient max-norm against 1e-10, the step norm
+                 against 1e-8 (|x| + 1e-8), |cost_change| against 1e-6 cost; None for the limit and the five invalid steps."""
+
+    def __new__(cls, trace, fs, rho, term, it, reason, deciding):
+        self = super().__new__(cls, (trace, fs, rho, term, it))
+        self.reason, self.deciding = reason, deciding
+        return self
+
+
+def solve(pb, O, state_update=True, fail_factorizations=0, invalid_steps=0):
+    """Returns a SolveResult: (trace list of dicts, final frame_state, final rho, termination, iterations) and the reason of the exit."""
+    return solve_dense(DenseProblem(pb, O), pb.frame_state.copy(), pb.lm_inv_depth.copy(), pb.max_iterations, state_update,
+                       fail_factorizations, invalid_steps)
+
+
+def solve_dense(D, fs, rho, max_iterations, state_update=True, fail_factorizations=0, invalid_steps=0):
+    """The loop itself, for any problem object with evaluate(fs, rho, user, jac) / plus / ambient / ncols.
+    fail_factorizations / invalid_steps: the fault injection of oracle_debug_fault_injection and pvio_hip_opts::debug_* -- the first n
+    factorizations count as failed, the first n steps that have a model decrease count as invalid."""
+    fail_left, invalid_left = fail_factorizations, invalid_steps
     user = fs.copy()
     best = (fs.copy(), rho.copy())
     trace = []
@@ -159,7 +179,7 @@ def solve_dense(D, fs, rho, max_iterations, state_update=True):
     grad_max = gmax(fs, rho, g_unscaled)
     x_norm = np.linalg.norm(D.ambient(fs, rho))
     min_cost = np.inf
-    it, success, term = 0, True, 1
+    it, success, term, reason, deciding = 0, True, 1, LIMIT, None
     rec = dict(cost=x_cost, cost_change=0.0, step_norm=0.0, relative_decrease=0.0, step_is_valid=1)
     diag = ghat = gn = None
     alpha = step_norm_dl = 0.0
@@ -172,13 +192,13 @@ def solve_dense(D, fs, rho, max_iterations, state_update=True):
         if success and state_update:
             user = best[0].copy()
         if it >= max_iterations:
-            term = 1
+            term, reason = 1, LIMIT
             break
         if success and grad_max <= 1e-10:
-            term = 0
+            term, reason, deciding = 0, GRADIENT, (grad_max, 1e-10)
             break
         if radius <= 1e-32:
-            term = 0
+            term, reason, deciding = 0, MIN_RADIUS, (radius, 1e-32)
             break
         it += 1
         success = False
@@ -193,10 +213,12 @@ def solve_dense(D, fs, rho, max_iterations, state_update=True):
             ok = False
             while mu < 1.0:
                 A = J.T @ J + np.diag(mu * diag * diag)
+                injected = fail_left > 0
+                fail_left -= injected
                 try:
                     Lc = np.linalg.cholesky(A)
                     y = np.linalg.solve(Lc.T, np.linalg.solve(Lc, J.T @ r))
-                    if np.all(np.isfinite(y)):
+                    if np.all(np.isfinite(y)) and not injected:
                         ok = True
                         break
                 except np.linalg.LinAlgError:
@@ -222,11 +244,14 @@ def solve_dense(D, fs, rho, max_iterations, state_update=True):
             step = step / diag
             mr = J @ step
             model_change = -mr @ (r + mr / 2.0)
-            rec["step_is_valid"] = int(model_change > 0)
-        if not ok or model_change <= 0:
+            valid = model_change > 0
+            if invalid_left > 0:
+                invalid_left, valid = invalid_left - 1, False
+            rec["step_is_valid"] = int(valid)
+        if not ok or not valid:
             invalid += 1
             if invalid >= 5:
-                term = 2
+                term, reason = 2, INVALID_STEPS
                 break
             mu *= 10.0
             reuse = False
@@ -239,11 +264,11 @@ def solve_dense(D, fs, rho, max_iterations, state_update=True):
             cand_cost = np.finfo(float).max
         rec["step_norm"] = np.linalg.norm(D.ambient(fs, rho) - D.ambient(cfs, crho))
         if rec["step_norm"] <= 1e-8 * (x_norm + 1e-8):
-            term = 0
+            term, reason, deciding = 0, PARAMETER, (rec["step_norm"], 1e-8 * (x_norm + 1e-8))
             break
         rec["cost_change"] = x_cost - cand_cost
         if abs(rec["cost_change"]) <= 1e-6 * x_cost:
-            term = 0
+            term, reason, deciding = 0, FUNCTION, (abs(rec["cost_change"]), 1e-6 * x_cost)
             break
         rel = rec["cost_change"] / model_change
         rec["relative_decrease"] = rel
@@ -266,7 +291,7 @@ def solve_dense(D, fs, rho, max_iterations, state_update=True):
             radius *= 0.5
             reuse = True
             rec["cost"] = cand_cost
-    return trace, best[0], best[1], term, it
+    return SolveResult(trace, best[0], best[1], term, it, reason, deciding)
 
 
 def marginalize(pb, O, fs, rho, victim):

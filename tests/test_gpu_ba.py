@@ -427,21 +427,27 @@ def test_gpu_window_sweep_compares_nearly_every_window():
     assert len(_SWEEP["skipped"]) <= 2, _SWEEP["skipped"]
 
 
+def poison_device_memory(poison):
+    """4 GB of device memory filled with `poison` and handed back to the driver: what a context created next allocates is carved from them
+    (also used by tests/test_solver_exits.py)"""
+    import torch
+    xs = [torch.full((64 * 1024 * 1024,), poison, dtype=torch.float64, device="cuda") for _ in range(8)]
+    torch.cuda.synchronize()
+    del xs
+    torch.cuda.empty_cache()
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("poison", [float("nan"), 1e300], ids=["nan", "1e300"])
 def test_gpu_solver_reads_nothing_it_did_not_write(oracle, poison):
     """A fresh context on device memory that a previous owner left full of NaN (or 1e300): 4 GB are filled and handed back to the
     driver right before the solver allocates, so that its buffers are carved from them.  Any scratch / padding / second-buffer
     word read before it is written would end in a different trace; the solves must equal the oracle's as usual.  (Fresh pages
     from the driver are zeroed, which is the other thing a first solve may meet: every other GPU test starts that way.)"""
-    import torch
     from pvio_amd.solver import HipContext
     for name in ("vio_small", "vision_partial", "vio_plane"):
         pb = ba_compare.make(oracle, **ba_compare.CASES[name])
-        xs = [torch.full((64 * 1024 * 1024,), poison, dtype=torch.float64, device="cuda") for _ in range(8)]
-        torch.cuda.synchronize()
-        del xs
-        torch.cuda.empty_cache()
-        torch.cuda.synchronize()
+        poison_device_memory(poison)
         ctx = HipContext(device=0)
         try:
             ba_compare.check_against_oracle(ctx, oracle, pb)
