@@ -61,14 +61,10 @@ BASolver::BASolver(int device, int rank, int world, bool use_graph) : device_(de
     (void)hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking);
     (void)hipEventCreate(&ev0_);
     (void)hipEventCreate(&ev1_);
-    (void)hipHostMalloc(&h_ctrl_, sizeof(Ctrl));
+    h_ctrl_ = static_cast<Ctrl *>(ctrl_pin_.reserve(sizeof(Ctrl), sizeof(Ctrl)));
 }
 BASolver::~BASolver() {
     invalidate_graph();
-    if (h_ctrl_) (void)hipHostFree(h_ctrl_);
-    if (h_stage_) (void)hipHostFree(h_stage_);
-    if (h_back_) (void)hipHostFree(h_back_);
-    if (h_pack_) (void)hipHostFree(h_pack_);
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -585,18 +581,14 @@ int BASolver::stage_inputs(const pvio_ba_problem *pb, const pvio_ba_state *st, c
         if (check(hipStreamSynchronize(stream_), "staging buffer still in flight")) return PVIO_ERR_HIP;
         stage_in_flight_ = false;
     }
-    if (staged > h_stage_cap_) {
-        if (h_stage_) (void)hipHostFree(h_stage_);
-        h_stage_ = nullptr, h_stage_cap_ = 0;
-        const size_t cap = staged + staged / 2; // (pinned host memory is the expensive allocation: headroom for the next windows of the sequence)
-        if (hipHostMalloc(&h_stage_, cap) != hipSuccess) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
-        h_stage_cap_ = cap;
-    }
+    // (pinned host memory is the expensive allocation: headroom for the next windows of the sequence)
+    char *h_stage = static_cast<char *>(h_stage_.reserve(staged, staged + staged / 2));
+    if (!h_stage && staged) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
     for (const auto &it : stage.items) {
-        if (it.src && it.bytes < kDirect) std::memcpy(static_cast<char *>(h_stage_) + it.off, it.src, it.bytes);
+        if (it.src && it.bytes < kDirect) std::memcpy(h_stage + it.off, it.src, it.bytes);
         *it.dst = slab + it.off;
     }
-    if (check(hipMemcpyAsync(slab, h_stage_, staged, hipMemcpyHostToDevice, stream_), "H2D inputs")) return PVIO_ERR_HIP;
+    if (check(hipMemcpyAsync(slab, h_stage, staged, hipMemcpyHostToDevice, stream_), "H2D inputs")) return PVIO_ERR_HIP;
     for (const auto &it : stage.items)
         if (it.src && it.bytes >= kDirect) {
             if (check(hipMemcpyAsync(slab + it.off, it.src, it.bytes, hipMemcpyHostToDevice, stream_), "H2D inputs")) return PVIO_ERR_HIP;
@@ -766,14 +758,9 @@ int BASolver::solve(pvio_ba_summary *sum, pvio_ba_kernel_times *prof, pvio_ba_st
     if (read_back) {
         bool grew = false;
         if (!dev(pool_, "result_pack", n_pack, &d_pack, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "result_pack");
-        if (n_pack > h_pack_cap_) {
-            if (h_pack_) (void)hipHostFree(h_pack_);
-            h_pack_ = nullptr, h_pack_cap_ = 0;
-            const size_t cap = n_pack + n_pack / 2;
-            if (hipHostMalloc(reinterpret_cast<void **>(&h_pack_), cap * sizeof(double)) != hipSuccess) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
-            h_pack_cap_ = cap;
-        }
+        if (!h_pack_.reserve(n_pack * sizeof(double), (n_pack + n_pack / 2) * sizeof(double))) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
     }
+    double *const h_pack = h_pack_.as<double>();
     // trace states are optional and live in a separate buffer so that bench runs do not pay for them
     const bool want_states = sum && sum->trace_states && sum->trace_capacity > 0;
     {
@@ -870,7 +857,7 @@ int BASolver::solve(pvio_ba_summary *sum, pvio_ba_kernel_times *prof, pvio_ba_st
         if (check(hipEventRecord(ev1_, stream_), "event")) return PVIO_ERR_HIP;
         if (read_back) { // speculative: all but never is the state machine still running after one replay (then this is repeated)
             if (check(launch_quality(v_, stream_, 1, nullptr, d_pack), "k_quality")) return PVIO_ERR_HIP;
-            if (check(hipMemcpyAsync(h_pack_, d_pack, n_pack * sizeof(double), hipMemcpyDeviceToHost, stream_), "results D2H")) return PVIO_ERR_HIP;
+            if (check(hipMemcpyAsync(h_pack, d_pack, n_pack * sizeof(double), hipMemcpyDeviceToHost, stream_), "results D2H")) return PVIO_ERR_HIP;
         }
         if (check(hipStreamSynchronize(stream_), "solve sync")) return PVIO_ERR_HIP;
         stage_in_flight_ = false;
@@ -942,10 +929,10 @@ int BASolver::solve(pvio_ba_summary *sum, pvio_ba_kernel_times *prof, pvio_ba_st
     }
     if (read_back) { // same semantics as download(): invalidated landmarks keep their old quality (bundle_adjustor.cpp:294)
         const size_t M = dm.M;
-        if (read_back->frame_state) std::memcpy(read_back->frame_state, h_pack_, Ns * 16 * sizeof(double));
-        if (M && read_back->lm_inv_depth) std::memcpy(read_back->lm_inv_depth, h_pack_ + Ns * 16, M * sizeof(double));
-        const double *q = h_pack_ + Ns * 16 + M;
-        const unsigned char *val = reinterpret_cast<const unsigned char *>(h_pack_ + Ns * 16 + 2 * M);
+        if (read_back->frame_state) std::memcpy(read_back->frame_state, h_pack, Ns * 16 * sizeof(double));
+        if (M && read_back->lm_inv_depth) std::memcpy(read_back->lm_inv_depth, h_pack + Ns * 16, M * sizeof(double));
+        const double *q = h_pack + Ns * 16 + M;
+        const unsigned char *val = reinterpret_cast<const unsigned char *>(h_pack + Ns * 16 + 2 * M);
         for (size_t l = 0; l < M; ++l) {
             if (read_back->lm_valid) read_back->lm_valid[l] = val[l];
             if (read_back->lm_quality && val[l]) read_back->lm_quality[l] = q[l];
@@ -1118,16 +1105,11 @@ int BASolver::marginalize(const pvio_ba_problem *pb, const pvio_ba_state *st, in
     const size_t n_back[8] = {nS + nV + kNumLinScal, Ns * 900, Ns * 30, Dp * Dp, Dp, Ns * 9, Ns * 3, ((size_t)dm.n_tasks + 1) / 2};
     size_t off_back[9] = {0};
     for (int k = 0; k < 8; ++k) off_back[k + 1] = off_back[k] + ((n_back[k] + 7) & ~(size_t)7);
-    if (off_back[8] > h_back_cap_) {
-        if (h_back_) (void)hipHostFree(h_back_);
-        h_back_ = nullptr, h_back_cap_ = 0;
-        const size_t cap = off_back[8] + off_back[8] / 2;
-        if (hipHostMalloc(reinterpret_cast<void **>(&h_back_), cap * sizeof(double)) != hipSuccess) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
-        h_back_cap_ = cap;
-    }
-    const double *red = h_back_ + off_back[0], *preH = h_back_ + off_back[1], *preg = h_back_ + off_back[2], *priH = h_back_ + off_back[3];
-    const double *prig = h_back_ + off_back[4], *rotH = h_back_ + off_back[5], *rotg = h_back_ + off_back[6];
-    const int32_t *tasks = reinterpret_cast<const int32_t *>(h_back_ + off_back[7]);
+    double *const h_back = static_cast<double *>(h_back_.reserve(off_back[8] * sizeof(double), (off_back[8] + off_back[8] / 2) * sizeof(double)));
+    if (!h_back) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+    const double *red = h_back + off_back[0], *preH = h_back + off_back[1], *preg = h_back + off_back[2], *priH = h_back + off_back[3];
+    const double *prig = h_back + off_back[4], *rotH = h_back + off_back[5], *rotg = h_back + off_back[6];
+    const int32_t *tasks = reinterpret_cast<const int32_t *>(h_back + off_back[7]);
     const void *src_back[8] = {v_.red, v_.pre_H, v_.pre_g, v_.prior_H, v_.prior_g, v_.rot_H, v_.rot_g, v_.task_desc};
     GatherArgs ga;
     for (int k = 0; k < 8; ++k) {
@@ -1141,7 +1123,7 @@ int BASolver::marginalize(const pvio_ba_problem *pb, const pvio_ba_state *st, in
         if (!dev(pool_, "marg_back", off_back[8], &d_back, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "marg_back");
     }
     if (check(launch_gather(ga, d_back, stream_), "k_gather")) return PVIO_ERR_HIP;
-    if (check(hipMemcpyAsync(h_back_, d_back, off_back[8] * sizeof(double), hipMemcpyDeviceToHost, stream_), "D2H")) return PVIO_ERR_HIP;
+    if (check(hipMemcpyAsync(h_back, d_back, off_back[8] * sizeof(double), hipMemcpyDeviceToHost, stream_), "D2H")) return PVIO_ERR_HIP;
     if (check(hipStreamSynchronize(stream_), "marginalize sync")) return PVIO_ERR_HIP;
     stage_in_flight_ = false;
     const auto tm2 = std::chrono::steady_clock::now();

@@ -7,6 +7,7 @@
 
 #include "../../include/pvio_hip.h"
 #include "ba_types.h"
+#include "hip_buffer.h"
 
 namespace pvba {
 
@@ -81,18 +82,16 @@ class BASolver {
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     DevicePool pool_;
     View v_{};
-    Ctrl *h_ctrl_ = nullptr; // pinned
+    pvhip::PinnedBuffer ctrl_pin_;
+    Ctrl *h_ctrl_ = nullptr; // the one Ctrl in ctrl_pin_ (pinned, allocated once by the constructor)
     bool uploaded_ = false;
     int solves_since_upload_ = 0;
     int cus_ = 0;
-    void *h_stage_ = nullptr; // pinned staging of one upload's inputs
-    size_t h_stage_cap_ = 0;
+    pvhip::PinnedBuffer h_stage_; // pinned staging of one upload's inputs
     bool stage_in_flight_ = false; // upload(may_return_early) left its staged copy queued; cleared by the next stream synchronization
-    double *h_back_ = nullptr; // pinned read-back of one marginalization pass
-    size_t h_back_cap_ = 0;    // in doubles
+    pvhip::PinnedBuffer h_back_; // pinned read-back of one marginalization pass (doubles)
     std::vector<double> marg_H_, marg_C_, marg_V_; // host work arrays of a marginalization (15N x 15N, twice 15(N-1) x 15(N-1))
-    double *h_pack_ = nullptr; // pinned: a solve's packed results (k_quality `pack`)
-    size_t h_pack_cap_ = 0;    // in doubles
+    pvhip::PinnedBuffer h_pack_; // pinned: a solve's packed results (k_quality `pack`, doubles)
     const double *fs_init_ = nullptr, *rho_init_ = nullptr; // initial state inside the inputs slab
     Ctrl h_ctrl_tmpl_{};                                    // what a solve's control block starts from (k_reset copies the device copy)
     Ctrl *d_ctrl_tmpl_ = nullptr;

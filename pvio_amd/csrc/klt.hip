@@ -1,9 +1,13 @@
-// klt.hip -- device-resident image front end: CLAHE, 4-level pyramid, Scharr derivatives, pyramidal Lucas-Kanade.
+// klt.hip -- device-resident image front end: undistortion, CLAHE, 4-level pyramid, Scharr derivatives, pyramidal Lucas-Kanade, Harris corner
+// detection, fundamental-matrix RANSAC.
 //
 // Replaces what the reference gets from OpenCV in
 //   OpenCvImage::preprocess       pvio-extra/src/pvio/extra/opencv_image.cpp:138-145  (CLAHE(6.0, 8x8) + buildOpticalFlowPyramid(21x21, 3, true))
 //   OpenCvImage::track_keypoints  opencv_image.cpp:88-109                             (calcOpticalFlowPyrLK + 20-px border kill)
-// The F-matrix RANSAC of :121-129 stays on the host adapter.
+//                                 opencv_image.cpp:113-129                            (findFundamentalMat(FM_RANSAC))
+//   OpenCvImage::detect_keypoints opencv_image.cpp:61, detector :183                  (goodFeaturesToTrack with the Harris measure)
+// Sections: the image kernels and the three forms of the LK search; the host side of images and tracking (one definition per buffer
+// layout first); corner detection, kernels then host; the RANSAC, kernel then host.
 //
 // HBM layout: every pyramid level is stored PADDED by kPad pixels on each side -- pixels with the BORDER_REFLECT_101
 // values OpenCV's pyramid carries, derivatives (int16 x 2, interleaved) with a zero border -- so that the LK kernel
@@ -65,9 +69,7 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 // ---- CLAHE ----------------------------------------------------------------------------------------------------------
 // one workgroup per tile: histogram (LDS atomics), clip + redistribute, cumulative LUT
 __global__ void __launch_bounds__(256) k_clahe_lut(const uint8_t *src, int w, int h, int tiles_x, int tiles_y, int tw, int th, int clip, uint8_t *lut) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+    PV_NO_CONTRACT
     __shared__ int hist[256];
     __shared__ int scan[256];
     __shared__ int s_clipped;
@@ -109,9 +111,7 @@ __global__ void __launch_bounds__(256) k_clahe_lut(const uint8_t *src, int w, in
 }
 
 __global__ void k_clahe_apply(const uint8_t *src, int w, int h, int tiles_x, int tiles_y, int tw, int th, const uint8_t *lut, LevelDesc out) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+    PV_NO_CONTRACT
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w || y >= h) return;
     const float inv_tw = 1.0f / (float)tw, inv_th = 1.0f / (float)th;
@@ -279,9 +279,7 @@ struct LkTplRaw {
     lk_drv_raw d0, d1;
 };
 __device__ __forceinline__ int lk_template_load(const LevelDesc &I, int level, float pxf, float pyf, int wy, int wx, LkTplRaw &t) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+    PV_NO_CONTRACT
     const float half = (kWin - 1) * 0.5f;
     const float sc = (float)(1. / (1 << level));
     const float px = pxf * sc - half, py = pyf * sc - half;
@@ -307,9 +305,7 @@ struct LkTpl {
     float A11, A12, A22, Dinv;
 };
 __device__ __forceinline__ int lk_template_form(const LkTplRaw &t, bool live, LkTpl &T) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+    PV_NO_CONTRACT
     const float FLT_SCALE = 1.f / (1 << 20);
     constexpr int W_BITS = LK_W_BITS;
     const int wA = t.w00 | (t.w01 << 16), wB = t.w10 | (t.w11 << 16); // (left, right) weight pairs of the two rows
@@ -349,9 +345,7 @@ __device__ __forceinline__ int lk_level_template(const LevelDesc &I, int level, 
     return skip; // template outside the image / degenerate gradient matrix
 }
 __device__ __forceinline__ void lk_level_search(const LevelDesc &J, int level, bool coarsest, const LkTpl &T, int skip, int lane, float &outx, float &outy, int &st) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+    PV_NO_CONTRACT
     const bool live = lane < kWin * 3;
     const int wy = live ? lane / 3 : 0, wx = live ? kRun * (lane - 3 * wy) : 0;
     const float half = (kWin - 1) * 0.5f, FLT_SCALE = 1.f / (1 << 20);
@@ -539,16 +533,98 @@ __global__ void __launch_bounds__(64 * kLkUnitWaves) k_lk_track_units(TrackArgs 
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
-static int level_sizes(int w, int h, int *ws, int *hs) {
-    int n = 0;
+// One definition per buffer layout: where every array lies in its slab or scratch block (byte offsets) and how large the whole is.  The methods
+// below take sizes, pointers and copy extents from these and nowhere else.
+
+// Pyramid slab of a w x h image: [raw pixels | CLAHE LUTs | level 0 image | level 0 derivatives | level 1 ...], every part on a 256-byte boundary.
+struct PyramidPlan {
+    int n_levels = 0;
+    int w[kLevels], h[kLevels], pitch[kLevels];
+    size_t raw, lut, img[kLevels], drv[kLevels], bytes = 0;
+};
+static PyramidPlan plan_pyramid(int w, int h) {
+    PyramidPlan p;
+    auto carve = [&p](size_t bytes) {
+        const size_t o = p.bytes;
+        p.bytes += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    p.raw = carve((size_t)w * h), p.lut = carve(64 * 256);
     for (int l = 0; l < kLevels; ++l) {
         if (l > 0) {
             w = (w + 1) / 2, h = (h + 1) / 2;
             if (w <= kWin || h <= kWin) break; // buildOpticalFlowPyramid stops when a level is not larger than the window
         }
-        ws[n] = w, hs[n] = h, ++n;
+        p.w[l] = w, p.h[l] = h, p.pitch[l] = (w + 2 * kPad + 63) & ~63;
+        p.img[l] = carve((size_t)(h + 2 * kPad) * p.pitch[l]);
+        p.drv[l] = carve((size_t)(h + 2 * kPad) * p.pitch[l] * 4);
+        p.n_levels = l + 1;
     }
-    return n;
+    return p;
+}
+
+// Track block of n points, the device buffer and its pinned mirror alike: [previous points | next points | status bytes].  One DMA in
+// ([previous | initial next] points), one out ([next points | status bytes]): four pageable copies cost more than the kernel.
+struct TrackBlock {
+    size_t xy_bytes, status_bytes; // one array: float[n][2], uint8[n]
+    size_t prev = 0, next, status; // where each lies
+    size_t h2d_bytes, d2h_bytes;   // the copy in starts at `prev`, the copy out at `next`
+    size_t bytes;                  // asked of the buffers
+    explicit TrackBlock(int n)
+        : xy_bytes((size_t)n * 8), status_bytes((size_t)n), next(xy_bytes), status(2 * xy_bytes), h2d_bytes(2 * xy_bytes), d2h_bytes(xy_bytes + status_bytes),
+          bytes((size_t)n * (2 * sizeof(float) * 2 + 1) + 64) {}
+};
+
+// Detection scratch of a w x h image: four float planes (the three covariance products, the response map), the candidate list (values, then
+// positions: `cap` of each) and three int scalars.  A quarter of the pixels is the most the 3 x 3 non-maximum suppression can produce.
+// Once the response map exists the covariance planes are dead and carry the data of the minimum-distance pre-filter: the xx plane the key map,
+// the xy plane the dominant map (a byte per pixel) and behind it the dominant flags (a byte per candidate), the yy plane the contested
+// candidates (values, then positions).
+struct DetectScratch {
+    size_t px;
+    int cap;
+    size_t bytes;
+    float *cxx = nullptr, *cxy = nullptr, *cyy = nullptr, *resp = nullptr, *cand_val = nullptr, *keymap = nullptr, *out_val = nullptr;
+    int *cand_pos = nullptr, *out_pos = nullptr, *scal = nullptr; // scal[0] max bits, [1] candidates, [2] contested candidates
+    uint8_t *dominant_map = nullptr, *dominant_flag = nullptr;
+    static constexpr size_t kScalBytes = 12;
+    DetectScratch(int w, int h) : px((size_t)w * h), cap((int)(px / 4 + 64)), bytes(px * 4 * sizeof(float) + (size_t)cap * 8 + 256) {}
+    size_t response_end() const { return px * 16; } // a buffer this large holds the response map of such an image
+    void bind(void *base) {
+        static_assert(sizeof(float) == 4 && sizeof(int) == 4, "plane arithmetic");
+        cxx = static_cast<float *>(base), cxy = cxx + px, cyy = cxy + px, resp = cyy + px, cand_val = resp + px;
+        cand_pos = reinterpret_cast<int *>(cand_val + cap), scal = cand_pos + cap;
+        keymap = cxx;
+        dominant_map = reinterpret_cast<uint8_t *>(cxy), dominant_flag = dominant_map + px;
+        out_val = cyy, out_pos = reinterpret_cast<int *>(cyy + cap);
+    }
+};
+// the device list the host walks (all candidates, or the contested ones) and the slot of DetectScratch::scal that holds its length
+struct DetectList { const float *val; const int *pos; int count_slot; };
+
+// RANSAC block of n matches and at most cap_h hypotheses per batch, one device block + its pinned mirror: [p | q | samples | counts | models | masks]
+struct FundBlock {
+    int nw; // 64-bit mask words per model
+    size_t p = 0, q, samples, counts, models, masks, bytes;
+    FundBlock(int n, int cap_h)
+        : nw((n + 63) / 64), q((size_t)n * 8), samples(q + (size_t)n * 8), counts((samples + (size_t)cap_h * 28 * 4 + 15) & ~(size_t)15), models(counts + (size_t)cap_h * 16),
+          masks(models + (size_t)cap_h * 27 * 8), bytes(masks + (size_t)cap_h * 3 * nw * 8) {}
+};
+
+// The launch form of the LK search, a pure function of the two switches, the device's size and the number of tracks.
+enum class LkKernel { kPerTrack, kLevels, kUnits };
+struct LkLaunch { LkKernel kernel; int grid, block; };
+static LkLaunch choose_lk_launch(int lk_form, int lk_blocks, int n_simds, int n) {
+    // more tracks than SIMDs: (track, level) units from a queue in LDS, a block of eight waves per CU (see k_lk_track_units); otherwise a wave per track
+    const int blocks = lk_blocks > 0 ? lk_blocks : n_simds / 4;
+    const bool units = lk_form == 2 && (n + blocks - 1) / blocks <= kLkMaxOwned;
+    // default: a workgroup per track and a wave per level up to three tracks per CU, a wave per track beyond -- same-box A/Bs of the mean of 50 launches
+    // (profiles/r6_klt_bench_ab.txt, bench.py's own point set): 150 tracks 22.2 -> 19.2 us, 300 tracks 25.5 -> 22.4 us; 600 tracks 23.3 -> 24.0,
+    // 1500 tracks 35.3 -> 36.2 (with five or six chains per CU the level waves of different tracks meet on the same SIMDs: nothing is gained)
+    const bool levels = lk_form == 0 ? (long)n * 4 <= 3L * n_simds : lk_form == 3;
+    if (units) return {LkKernel::kUnits, std::min(blocks, n), 64 * kLkUnitWaves};
+    if (levels) return {LkKernel::kLevels, n, 64 * kLevels};
+    return {LkKernel::kPerTrack, (n + 3) / 4, 256};
 }
 
 Klt::Klt(int device) : device_(device) {
@@ -562,42 +638,29 @@ Klt::Klt(int device) : device_(device) {
     (void)hipEventCreate(&ev1_);
 }
 Klt::~Klt() {
-    if (d_pts_) (void)hipFree(d_pts_);
-    if (d_det_) (void)hipFree(d_det_);
-    if (d_src_) (void)hipFree(d_src_);
-    if (h_pts_) (void)hipHostFree(h_pts_);
-    if (d_fm_) (void)hipFree(d_fm_);
-    if (h_fm_) (void)hipHostFree(h_fm_);
-    if (det_host_) (void)hipHostFree(det_host_);
     for (auto &s : slab_pool_) (void)hipFree(s.second);
-    if (staging_) (void)hipHostFree(staging_);
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
     if (stream_) (void)hipStreamDestroy(stream_);
 }
+int Klt::fail(int code, const char *msg) {
+    err_ = msg;
+    return code;
+}
 
 int Klt::create_undistort(const int16_t *map_xy, const uint16_t *map_frac, int w, int h, Undistort **out) {
-    if (!map_xy || !map_frac || w < 1 || h < 1) {
-        err_ = "bad undistortion map";
-        return PVIO_ERR_INVALID_ARGUMENT;
-    }
+    if (!map_xy || !map_frac || w < 1 || h < 1) return fail(PVIO_ERR_INVALID_ARGUMENT, "bad undistortion map");
     (void)hipSetDevice(device_);
-    Undistort *u = new Undistort();
-    u->w = w, u->h = h, u->xy = nullptr, u->frac = nullptr;
     const size_t n = (size_t)w * h;
     void *slab = nullptr;
-    if (hipMalloc(&slab, n * 6) != hipSuccess) {
-        delete u;
-        err_ = "hipMalloc failed";
-        return PVIO_ERR_OUT_OF_MEMORY;
-    }
+    if (hipMalloc(&slab, n * 6) != hipSuccess) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipMalloc failed");
+    Undistort *u = new Undistort();
+    u->w = w, u->h = h;
     u->xy = static_cast<int16_t *>(slab);
     u->frac = reinterpret_cast<uint16_t *>(static_cast<char *>(slab) + n * 4);
     if (hipMemcpy(u->xy, map_xy, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(u->frac, map_frac, n * 2, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(slab);
-        delete u;
-        err_ = "H2D failed";
-        return PVIO_ERR_HIP;
+        release_undistort(u);
+        return fail(PVIO_ERR_HIP, "H2D failed");
     }
     *out = u;
     return PVIO_OK;
@@ -608,87 +671,48 @@ void Klt::release_undistort(Undistort *u) {
     delete u;
 }
 
-int Klt::create_image(const uint8_t *pixels, int sw, int sh, int stride, bool clahe, Image **out, const Undistort *ud) {
-    // with an undistortion map the pyramid has the MAP's size and the uploaded pixels are only the source of the remap
-    const int w = ud ? ud->w : sw, h = ud ? ud->h : sh;
-    if (w < 2 * kWin || h < 2 * kWin || sw < 1 || sh < 1 || stride < sw) {
-        err_ = "image too small / bad stride";
-        return PVIO_ERR_INVALID_ARGUMENT;
-    }
-    (void)hipSetDevice(device_);
+// a slab of the plan's size from the pool of released ones, or a new one; the image's pointers into it.  nullptr: no memory
+Image *Klt::take_slab(const PyramidPlan &plan) {
+    void *slab = nullptr;
+    for (size_t i = 0; i < slab_pool_.size() && !slab; ++i)
+        if (slab_pool_[i].first == plan.bytes) {
+            slab = slab_pool_[i].second;
+            slab_pool_.erase(slab_pool_.begin() + i);
+        }
+    if (!slab && hipMalloc(&slab, plan.bytes) != hipSuccess) return nullptr;
     Image *im = new Image();
     std::memset(im, 0, sizeof *im);
-    im->w = w, im->h = h;
-    int ws[kLevels], hs[kLevels];
-    im->n_levels = level_sizes(w, h, ws, hs);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    size_t o_raw = carve((size_t)w * h), o_lut = carve(64 * 256), o_img[kLevels], o_drv[kLevels];
-    for (int l = 0; l < im->n_levels; ++l) {
-        im->lv[l].w = ws[l], im->lv[l].h = hs[l];
-        im->lv[l].pitch = (ws[l] + 2 * kPad + 63) & ~63;
-        o_img[l] = carve((size_t)(hs[l] + 2 * kPad) * im->lv[l].pitch);
-        o_drv[l] = carve((size_t)(hs[l] + 2 * kPad) * im->lv[l].pitch * 4);
+    char *base = static_cast<char *>(slab);
+    im->w = plan.w[0], im->h = plan.h[0], im->n_levels = plan.n_levels;
+    im->slab = slab, im->slab_bytes = plan.bytes;
+    im->raw = reinterpret_cast<uint8_t *>(base + plan.raw);
+    im->lut = reinterpret_cast<uint8_t *>(base + plan.lut);
+    for (int l = 0; l < plan.n_levels; ++l) {
+        im->lv[l].w = plan.w[l], im->lv[l].h = plan.h[l], im->lv[l].pitch = plan.pitch[l];
+        im->lv[l].img = reinterpret_cast<uint8_t *>(base + plan.img[l]);
+        im->lv[l].drv = reinterpret_cast<int16_t *>(base + plan.drv[l]);
     }
-    im->slab_bytes = off;
-    for (size_t i = 0; i < slab_pool_.size(); ++i)
-        if (slab_pool_[i].first == off) {
-            im->slab = slab_pool_[i].second;
-            slab_pool_.erase(slab_pool_.begin() + i);
-            break;
-        }
-    if (!im->slab && hipMalloc(&im->slab, off) != hipSuccess) {
-        delete im;
-        err_ = "hipMalloc failed";
-        return PVIO_ERR_OUT_OF_MEMORY;
-    }
-    char *base = static_cast<char *>(im->slab);
-    im->raw = reinterpret_cast<uint8_t *>(base + o_raw);
-    im->lut = reinterpret_cast<uint8_t *>(base + o_lut);
-    for (int l = 0; l < im->n_levels; ++l) {
-        im->lv[l].img = reinterpret_cast<uint8_t *>(base + o_img[l]);
-        im->lv[l].drv = reinterpret_cast<int16_t *>(base + o_drv[l]);
-    }
-    // derivative borders are BORDER_CONSTANT zeros; image borders are written by k_border
-    (void)hipMemsetAsync(im->slab, 0, off, stream_);
-    // pixels go through a pinned staging buffer (packed rows): the copy is a real asynchronous DMA then
-    if ((size_t)sw * sh > staging_cap_) {
-        if (staging_) (void)hipHostFree(staging_);
-        staging_ = nullptr, staging_cap_ = 0;
-        if (hipHostMalloc(&staging_, (size_t)sw * sh) != hipSuccess) {
-            release_image(im);
-            err_ = "hipHostMalloc failed";
-            return PVIO_ERR_OUT_OF_MEMORY;
-        }
-        staging_cap_ = (size_t)sw * sh;
-    }
-    for (int y = 0; y < sh; ++y) std::memcpy(static_cast<uint8_t *>(staging_) + (size_t)y * sw, pixels + (size_t)y * stride, sw);
-    const uint8_t *src = static_cast<const uint8_t *>(staging_);
-    uint8_t *d_src = im->raw; // distorted pixels land in a scratch buffer, the remap writes im->raw
-    if (ud) {
-        if ((size_t)sw * sh > src_cap_) {
-            if (d_src_) (void)hipFree(d_src_);
-            d_src_ = nullptr, src_cap_ = 0;
-            if (hipMalloc(&d_src_, (size_t)sw * sh) != hipSuccess) {
-                release_image(im);
-                err_ = "hipMalloc failed";
-                return PVIO_ERR_OUT_OF_MEMORY;
-            }
-            src_cap_ = (size_t)sw * sh;
-        }
-        d_src = static_cast<uint8_t *>(d_src_);
-    }
-    if (hipMemcpyAsync(d_src, src, (size_t)sw * sh, hipMemcpyHostToDevice, stream_) != hipSuccess) {
-        release_image(im);
-        err_ = "H2D failed";
-        return PVIO_ERR_HIP;
-    }
+    return im;
+}
+
+// The pixels go through a pinned staging buffer (packed rows): the copy is a real asynchronous DMA then.  They land in `raw`, the image's own
+// plane -- or, when they still have to be undistorted, in a scratch buffer that the remap reads and writes `raw` from.  *d_src: where they are.
+int Klt::stage_pixels(const uint8_t *pixels, int sw, int sh, int stride, bool undistorted, uint8_t *raw, const uint8_t **d_src) {
+    const size_t bytes = (size_t)sw * sh;
+    uint8_t *host = static_cast<uint8_t *>(staging_.reserve(bytes, bytes));
+    if (!host) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+    for (int y = 0; y < sh; ++y) std::memcpy(host + (size_t)y * sw, pixels + (size_t)y * stride, sw);
+    uint8_t *dst = undistorted ? static_cast<uint8_t *>(d_src_.reserve(bytes, bytes)) : raw;
+    if (!dst) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipMalloc failed");
+    if (hipMemcpyAsync(dst, host, bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) return fail(PVIO_ERR_HIP, "H2D failed");
+    *d_src = dst;
+    return PVIO_OK;
+}
+
+static void enqueue_pyramid(hipStream_t stream, Image *im, bool clahe, const Undistort *ud, const uint8_t *d_src, int sw, int sh) {
+    const int w = im->w, h = im->h;
     const dim3 blk(256);
-    if (ud) hipLaunchKernelGGL(k_remap, dim3((w + 255) / 256, h), blk, 0, stream_, (const uint8_t *)d_src, sw, sh, (const int16_t *)ud->xy, (const uint16_t *)ud->frac, w, h, im->raw);
+    if (ud) hipLaunchKernelGGL(k_remap, dim3((w + 255) / 256, h), blk, 0, stream, d_src, sw, sh, (const int16_t *)ud->xy, (const uint16_t *)ud->frac, w, h, im->raw);
     if (clahe) {
         const int tiles = 8;
         int ew = w, eh = h;
@@ -696,22 +720,39 @@ int Klt::create_image(const uint8_t *pixels, int sw, int sh, int stride, bool cl
         const int tw = ew / tiles, th = eh / tiles;
         int clip = (int)(6.0 * (tw * th) / 256);
         if (clip < 1) clip = 1;
-        hipLaunchKernelGGL(k_clahe_lut, dim3(tiles * tiles), blk, 0, stream_, (const uint8_t *)im->raw, w, h, tiles, tiles, tw, th, clip, im->lut);
-        hipLaunchKernelGGL(k_clahe_apply, dim3((w + 255) / 256, h), blk, 0, stream_, (const uint8_t *)im->raw, w, h, tiles, tiles, tw, th,
+        hipLaunchKernelGGL(k_clahe_lut, dim3(tiles * tiles), blk, 0, stream, (const uint8_t *)im->raw, w, h, tiles, tiles, tw, th, clip, im->lut);
+        hipLaunchKernelGGL(k_clahe_apply, dim3((w + 255) / 256, h), blk, 0, stream, (const uint8_t *)im->raw, w, h, tiles, tiles, tw, th,
                            (const uint8_t *)im->lut, im->lv[0]);
     } else {
-        hipLaunchKernelGGL(k_copy_level0, dim3((w + 255) / 256, h), blk, 0, stream_, (const uint8_t *)im->raw, w, h, im->lv[0]);
+        hipLaunchKernelGGL(k_copy_level0, dim3((w + 255) / 256, h), blk, 0, stream, (const uint8_t *)im->raw, w, h, im->lv[0]);
     }
     for (int l = 0; l < im->n_levels; ++l) {
         const LevelDesc &L = im->lv[l];
-        hipLaunchKernelGGL(k_border, dim3((L.w + 2 * kPad + 255) / 256, L.h + 2 * kPad), blk, 0, stream_, L);
-        hipLaunchKernelGGL(k_scharr, dim3((L.w + 255) / 256, L.h), blk, 0, stream_, L);
-        if (l + 1 < im->n_levels) hipLaunchKernelGGL(k_pyr_down, dim3((im->lv[l + 1].w + 255) / 256, im->lv[l + 1].h), blk, 0, stream_, L, im->lv[l + 1]);
+        hipLaunchKernelGGL(k_border, dim3((L.w + 2 * kPad + 255) / 256, L.h + 2 * kPad), blk, 0, stream, L);
+        hipLaunchKernelGGL(k_scharr, dim3((L.w + 255) / 256, L.h), blk, 0, stream, L);
+        if (l + 1 < im->n_levels) hipLaunchKernelGGL(k_pyr_down, dim3((im->lv[l + 1].w + 255) / 256, im->lv[l + 1].h), blk, 0, stream, L, im->lv[l + 1]);
     }
-    if (hipStreamSynchronize(stream_) != hipSuccess || hipGetLastError() != hipSuccess) {
+}
+
+int Klt::create_image(const uint8_t *pixels, int sw, int sh, int stride, bool clahe, Image **out, const Undistort *ud) {
+    // with an undistortion map the pyramid has the MAP's size and the uploaded pixels are only the source of the remap
+    const int w = ud ? ud->w : sw, h = ud ? ud->h : sh;
+    if (w < 2 * kWin || h < 2 * kWin || sw < 1 || sh < 1 || stride < sw) return fail(PVIO_ERR_INVALID_ARGUMENT, "image too small / bad stride");
+    (void)hipSetDevice(device_);
+    const PyramidPlan plan = plan_pyramid(w, h);
+    Image *im = take_slab(plan);
+    if (!im) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipMalloc failed");
+    // derivative borders are BORDER_CONSTANT zeros; image borders are written by k_border
+    (void)hipMemsetAsync(im->slab, 0, plan.bytes, stream_);
+    const uint8_t *d_src = nullptr;
+    int rc = stage_pixels(pixels, sw, sh, stride, ud != nullptr, im->raw, &d_src);
+    if (rc == PVIO_OK) {
+        enqueue_pyramid(stream_, im, clahe, ud, d_src, sw, sh);
+        if (hipStreamSynchronize(stream_) != hipSuccess || hipGetLastError() != hipSuccess) rc = fail(PVIO_ERR_HIP, "pyramid kernels failed");
+    }
+    if (rc != PVIO_OK) {
         release_image(im);
-        err_ = "pyramid kernels failed";
-        return PVIO_ERR_HIP;
+        return rc;
     }
     *out = im;
     return PVIO_OK;
@@ -748,62 +789,31 @@ int Klt::download_level(const Image *img, int level, uint8_t *pixels, int16_t *d
 }
 
 int Klt::track(const Image *prev, const Image *next, int n, const float *prev_xy, float *next_xy, uint8_t *status) {
-    if (prev->w != next->w || prev->h != next->h) {
-        err_ = "image sizes differ";
-        return PVIO_ERR_INVALID_ARGUMENT;
-    }
+    if (prev->w != next->w || prev->h != next->h) return fail(PVIO_ERR_INVALID_ARGUMENT, "image sizes differ");
     last_ms_ = 0;
     if (n == 0) return PVIO_OK;
     (void)hipSetDevice(device_);
-    const size_t need = (size_t)n * (2 * sizeof(float) * 2 + 1) + 64;
-    if (need > pts_cap_) {
-        if (d_pts_) (void)hipFree(d_pts_);
-        d_pts_ = nullptr;
-        if (hipMalloc(&d_pts_, need * 2) != hipSuccess) {
-            pts_cap_ = 0;
-            err_ = "hipMalloc failed";
-            return PVIO_ERR_OUT_OF_MEMORY;
-        }
-        pts_cap_ = 0; // the capacity counts only once BOTH buffers exist
-        if (h_pts_) (void)hipHostFree(h_pts_);
-        h_pts_ = nullptr;
-        if (hipHostMalloc(&h_pts_, need * 2) != hipSuccess) {
-            h_pts_ = nullptr;
-            err_ = "hipHostMalloc failed";
-            return PVIO_ERR_OUT_OF_MEMORY;
-        }
-        pts_cap_ = need * 2;
-    }
-    float *d_prev = static_cast<float *>(d_pts_), *d_next = d_prev + 2 * (size_t)n;
-    uint8_t *d_st = reinterpret_cast<uint8_t *>(d_next + 2 * (size_t)n);
+    const TrackBlock tb(n);
+    char *db = static_cast<char *>(d_pts_.reserve(tb.bytes, 2 * tb.bytes));
+    if (!db) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipMalloc failed");
+    char *hb = static_cast<char *>(h_pts_.reserve(tb.bytes, 2 * tb.bytes));
+    if (!hb) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
     TrackArgs a;
     a.n = n, a.n_levels = std::min(prev->n_levels, next->n_levels);
     for (int l = 0; l < a.n_levels; ++l) a.prev[l] = prev->lv[l], a.next[l] = next->lv[l];
-    a.prev_xy = d_prev, a.next_xy = d_next, a.status = d_st;
-    // one DMA in ([previous | initial next] points), one out ([next points | status bytes]) through a pinned buffer laid out
-    // like the device one: four pageable copies cost more than the kernel
-    char *hp = static_cast<char *>(h_pts_);
-    std::memcpy(hp, prev_xy, (size_t)n * 8), std::memcpy(hp + (size_t)n * 8, next_xy, (size_t)n * 8);
-    bool ok = hipMemcpyAsync(d_prev, hp, (size_t)n * 16, hipMemcpyHostToDevice, stream_) == hipSuccess;
-    // more tracks than SIMDs: (track, level) units from a queue in LDS, a block of eight waves per CU (see k_lk_track_units); otherwise a wave per track
-    const int blocks = lk_blocks_ > 0 ? lk_blocks_ : n_simds_ / 4;
-    const bool units = lk_form_ == 2 && (n + blocks - 1) / blocks <= kLkMaxOwned;
-    // default: a workgroup per track and a wave per level up to three tracks per CU, a wave per track beyond -- same-box A/Bs of the mean of 50 launches
-    // (profiles/r6_klt_bench_ab.txt, bench.py's own point set): 150 tracks 22.2 -> 19.2 us, 300 tracks 25.5 -> 22.4 us; 600 tracks 23.3 -> 24.0,
-    // 1500 tracks 35.3 -> 36.2 (with five or six chains per CU the level waves of different tracks meet on the same SIMDs: nothing is gained)
-    const bool levels = lk_form_ == 0 ? (long)n * 4 <= 3L * n_simds_ : lk_form_ == 3;
+    a.prev_xy = reinterpret_cast<const float *>(db + tb.prev), a.next_xy = reinterpret_cast<float *>(db + tb.next), a.status = reinterpret_cast<uint8_t *>(db + tb.status);
+    std::memcpy(hb + tb.prev, prev_xy, tb.xy_bytes), std::memcpy(hb + tb.next, next_xy, tb.xy_bytes);
+    bool ok = hipMemcpyAsync(db + tb.prev, hb + tb.prev, tb.h2d_bytes, hipMemcpyHostToDevice, stream_) == hipSuccess;
+    const LkLaunch form = choose_lk_launch(lk_form_, lk_blocks_, n_simds_, n);
     (void)hipEventRecord(ev0_, stream_);
-    if (units) hipLaunchKernelGGL(k_lk_track_units, dim3(std::min(blocks, n)), dim3(64 * kLkUnitWaves), 0, stream_, a);
-    else if (levels) hipLaunchKernelGGL(k_lk_track_levels, dim3(n), dim3(64 * kLevels), 0, stream_, a);
-    else hipLaunchKernelGGL(k_lk_track, dim3((n + 3) / 4), dim3(256), 0, stream_, a);
+    if (form.kernel == LkKernel::kUnits) hipLaunchKernelGGL(k_lk_track_units, dim3(form.grid), dim3(form.block), 0, stream_, a);
+    else if (form.kernel == LkKernel::kLevels) hipLaunchKernelGGL(k_lk_track_levels, dim3(form.grid), dim3(form.block), 0, stream_, a);
+    else hipLaunchKernelGGL(k_lk_track, dim3(form.grid), dim3(form.block), 0, stream_, a);
     (void)hipEventRecord(ev1_, stream_);
-    ok = ok && hipMemcpyAsync(hp + (size_t)n * 8, d_next, (size_t)n * 9, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+    ok = ok && hipMemcpyAsync(hb + tb.next, db + tb.next, tb.d2h_bytes, hipMemcpyDeviceToHost, stream_) == hipSuccess;
     ok = ok && hipStreamSynchronize(stream_) == hipSuccess && hipGetLastError() == hipSuccess;
-    if (!ok) {
-        err_ = "klt track failed";
-        return PVIO_ERR_HIP;
-    }
-    std::memcpy(next_xy, hp + (size_t)n * 8, (size_t)n * 8), std::memcpy(status, hp + (size_t)n * 16, (size_t)n);
+    if (!ok) return fail(PVIO_ERR_HIP, "klt track failed");
+    std::memcpy(next_xy, hb + tb.next, tb.xy_bytes), std::memcpy(status, hb + tb.status, tb.status_bytes);
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ev0_, ev1_);
     last_ms_ = ms;
@@ -814,9 +824,7 @@ int Klt::track(const Image *prev, const Image *next, int n, const float *prev_xy
 // Streaming image kernels over level 0 (the CLAHE output, padded with its REFLECT_101 border); the float operations
 // follow ONE fixed order (stated in oracle/oracle_gftt.cpp) so that the response map is reproducible bit for bit.
 __global__ void __launch_bounds__(256) k_harris_cov(LevelDesc L, float *cxx, float *cxy, float *cyy) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+    PV_NO_CONTRACT
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= L.w) return;
     const uint8_t *p = L.img + (size_t)(y + kPad) * L.pitch + (x + kPad);
@@ -830,9 +838,7 @@ __global__ void __launch_bounds__(256) k_harris_cov(LevelDesc L, float *cxx, flo
 }
 
 __global__ void __launch_bounds__(256) k_harris_response(int w, int h, const float *cxx, const float *cxy, const float *cyy, float *resp, int *max_bits) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+    PV_NO_CONTRACT
     __shared__ float smax[4];
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     float r = -INFINITY;
@@ -868,9 +874,7 @@ __global__ void __launch_bounds__(256) k_harris_response(int w, int h, const flo
 // keymap != nullptr: every pixel also gets its candidate response (0 = not a candidate) for the dominance filter below
 __global__ void __launch_bounds__(256) k_harris_collect(int w, int h, const float *resp, const int *max_bits, float quality, int cap, int *count, float *cand_val,
                                                         int *cand_pos, float *keymap) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+    PV_NO_CONTRACT
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (keymap && x < w) keymap[(size_t)y * w + x] = 0.0f;
     if (x < 1 || x >= w - 1 || y < 1 || y >= h - 1) return;
@@ -948,106 +952,79 @@ __global__ void __launch_bounds__(256) k_corner_survivors(int w, int h, const ui
     }
 }
 
-int Klt::detect(const Image *img, int max_corners, double quality, double min_distance, float *xy, float *response, int *n_out) {
-    *n_out = 0;
-    (void)hipSetDevice(device_);
-    const int w = img->w, h = img->h;
-    const size_t px = (size_t)w * h;
-    const int cap = (int)(px / 4 + 64);
-    const size_t need = px * 4 * sizeof(float) + (size_t)cap * 8 + 256;
-    if (need > det_cap_) {
-        if (d_det_) (void)hipFree(d_det_);
-        d_det_ = nullptr;
-        if (hipMalloc(&d_det_, need) != hipSuccess) {
-            det_cap_ = 0;
-            err_ = "hipMalloc failed";
-            return PVIO_ERR_OUT_OF_MEMORY;
-        }
-        det_cap_ = need;
-    }
-    float *cxx = static_cast<float *>(d_det_), *cxy = cxx + px, *cyy = cxy + px, *resp = cyy + px, *cand_val = resp + px;
-    int *cand_pos = reinterpret_cast<int *>(cand_val + cap), *scal = cand_pos + cap; // scal[0] = max bits, scal[1] = count
-    (void)hipMemsetAsync(scal, 0, 12, stream_); // [0] max bits, [1] candidates, [2] contested candidates
+// response map, then the candidates the host has to walk: all of them, or -- with a minimum distance -- the contested ones
+static DetectList enqueue_detect(hipStream_t stream, const Image *img, const DetectScratch &s, double quality, double min_distance) {
+    const int w = img->w, h = img->h, cap = s.cap;
+    const bool filter = min_distance >= 1;
+    (void)hipMemsetAsync(s.scal, 0, DetectScratch::kScalBytes, stream);
     const dim3 grid((w + 255) / 256, h), blk(256);
-    hipLaunchKernelGGL(k_harris_cov, grid, blk, 0, stream_, img->lv[0], cxx, cxy, cyy);
-    hipLaunchKernelGGL(k_harris_response, grid, blk, 0, stream_, w, h, (const float *)cxx, (const float *)cxy, (const float *)cyy, resp, scal);
-    const float *list_val = cand_val;
-    const int *list_pos = cand_pos;
-    int count_slot = 1;
-    if (min_distance >= 1) {
-        // all candidates -> list + key map (the xx plane is dead by now) -> dominant flags / map (the xy plane) -> contested
-        // candidates, compacted into the yy plane
-        float *keymap = cxx;
-        uint8_t *dominant_map = reinterpret_cast<uint8_t *>(cxy), *dominant_flag = dominant_map + px;
-        float *out_val = cyy;
-        int *out_pos = reinterpret_cast<int *>(cyy + cap);
-        static_assert(sizeof(float) == 4, "plane arithmetic");
-        const int R = (int)std::ceil(min_distance);
-        const double md2 = min_distance * min_distance; // compared in double like the host selection
-        hipLaunchKernelGGL(k_harris_collect, grid, blk, 0, stream_, w, h, (const float *)resp, (const int *)scal, (float)quality, cap, scal + 1, cand_val, cand_pos,
-                           keymap);
-        (void)hipMemsetAsync(dominant_map, 0, px, stream_);
-        const dim3 lgrid(std::min((cap + 3) / 4, 2048)); // the kernels loop: the candidate count is only known on the device
-        hipLaunchKernelGGL(k_corner_dominant, lgrid, blk, 0, stream_, w, h, (const float *)keymap, (const int *)(scal + 1), (const float *)cand_val,
-                           (const int *)cand_pos, cap, R, md2, dominant_map, dominant_flag);
-        hipLaunchKernelGGL(k_corner_survivors, lgrid, blk, 0, stream_, w, h, (const uint8_t *)dominant_map, (const uint8_t *)dominant_flag, (const int *)(scal + 1),
-                           (const float *)cand_val, (const int *)cand_pos, cap, R, md2, scal + 2, out_val, out_pos);
-        list_val = out_val, list_pos = out_pos, count_slot = 2;
-    } else {
-        hipLaunchKernelGGL(k_harris_collect, grid, blk, 0, stream_, w, h, (const float *)resp, (const int *)scal, (float)quality, cap, scal + 1, cand_val, cand_pos,
-                           (float *)nullptr);
-    }
-    static const bool timing = getenv("PVIO_KLT_TIMING") != nullptr; // diagnostics: where a detect() call spends its time
-    const auto tt0 = std::chrono::steady_clock::now();
-    // counts and a first slice of the list come back together (one synchronization); a longer list costs a second round
+    hipLaunchKernelGGL(k_harris_cov, grid, blk, 0, stream, img->lv[0], s.cxx, s.cxy, s.cyy);
+    hipLaunchKernelGGL(k_harris_response, grid, blk, 0, stream, w, h, (const float *)s.cxx, (const float *)s.cxy, (const float *)s.cyy, s.resp, s.scal);
+    hipLaunchKernelGGL(k_harris_collect, grid, blk, 0, stream, w, h, (const float *)s.resp, (const int *)s.scal, (float)quality, cap, s.scal + 1, s.cand_val, s.cand_pos,
+                       filter ? s.keymap : (float *)nullptr);
+    if (!filter) return {s.cand_val, s.cand_pos, 1};
+    // all candidates -> list + key map -> dominant flags / map -> contested candidates, compacted (DetectScratch: which dead plane carries what)
+    const int R = (int)std::ceil(min_distance);
+    const double md2 = min_distance * min_distance; // compared in double like the host selection
+    (void)hipMemsetAsync(s.dominant_map, 0, s.px, stream);
+    const dim3 lgrid(std::min((cap + 3) / 4, 2048)); // the kernels loop: the candidate count is only known on the device
+    hipLaunchKernelGGL(k_corner_dominant, lgrid, blk, 0, stream, w, h, (const float *)s.keymap, (const int *)(s.scal + 1), (const float *)s.cand_val,
+                       (const int *)s.cand_pos, cap, R, md2, s.dominant_map, s.dominant_flag);
+    hipLaunchKernelGGL(k_corner_survivors, lgrid, blk, 0, stream, w, h, (const uint8_t *)s.dominant_map, (const uint8_t *)s.dominant_flag, (const int *)(s.scal + 1),
+                       (const float *)s.cand_val, (const int *)s.cand_pos, cap, R, md2, s.scal + 2, s.out_val, s.out_pos);
+    return {s.out_val, s.out_pos, 2};
+}
+
+// The list comes to the host: counts and a first slice of it together (one synchronization); a longer list costs a second round.
+// *n_all: how many candidates there were before the pre-filter.
+int Klt::fetch_candidates(const DetectScratch &s, const DetectList &list, std::vector<float> &val, std::vector<int> &pos, int *n_all) {
     constexpr int kFirst = 4096;
-    if (!det_host_) {
-        if (hipHostMalloc(&det_host_, 16 + (size_t)kFirst * 8) != hipSuccess) {
-            err_ = "hipHostMalloc failed";
-            return PVIO_ERR_OUT_OF_MEMORY;
-        }
-    }
-    int *hs = static_cast<int *>(det_host_);
+    constexpr size_t kHostBytes = 16 + (size_t)kFirst * 8; // [4 ints | kFirst values | kFirst positions]
+    int *hs = static_cast<int *>(det_host_.reserve(kHostBytes, kHostBytes));
+    if (!hs) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
     float *h_val = reinterpret_cast<float *>(hs + 4);
     int *h_pos = reinterpret_cast<int *>(h_val + kFirst);
-    const int first = std::min(kFirst, cap);
-    bool ok = hipMemcpyAsync(hs, scal, 12, hipMemcpyDeviceToHost, stream_) == hipSuccess;
-    ok = ok && hipMemcpyAsync(h_val, list_val, (size_t)first * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
-    ok = ok && hipMemcpyAsync(h_pos, list_pos, (size_t)first * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+    const int first = std::min(kFirst, s.cap);
+    bool ok = hipMemcpyAsync(hs, s.scal, DetectScratch::kScalBytes, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+    ok = ok && hipMemcpyAsync(h_val, list.val, (size_t)first * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+    ok = ok && hipMemcpyAsync(h_pos, list.pos, (size_t)first * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
     ok = ok && hipStreamSynchronize(stream_) == hipSuccess && hipGetLastError() == hipSuccess;
-    if (ok && hs[1] > cap) {
-        err_ = "too many corner candidates"; // a quarter of the pixels: the 3 x 3 non-maximum suppression cannot produce more
-        return PVIO_ERR_UNSUPPORTED;
-    }
-    const int nc = ok ? std::min(hs[count_slot], cap) : 0;
-    std::vector<float> val((size_t)nc);
-    std::vector<int> pos((size_t)nc);
+    // a quarter of the pixels: the 3 x 3 non-maximum suppression cannot produce more
+    if (ok && hs[1] > s.cap) return fail(PVIO_ERR_UNSUPPORTED, "too many corner candidates");
+    const int nc = ok ? std::min(hs[list.count_slot], s.cap) : 0;
+    val.resize((size_t)nc), pos.resize((size_t)nc);
     if (ok && nc > 0) {
         const int got = std::min(nc, first);
         std::memcpy(val.data(), h_val, (size_t)got * 4), std::memcpy(pos.data(), h_pos, (size_t)got * 4);
         if (nc > got) {
-            ok = hipMemcpyAsync(val.data() + got, list_val + got, (size_t)(nc - got) * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
-            ok = ok && hipMemcpyAsync(pos.data() + got, list_pos + got, (size_t)(nc - got) * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+            ok = hipMemcpyAsync(val.data() + got, list.val + got, (size_t)(nc - got) * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+            ok = ok && hipMemcpyAsync(pos.data() + got, list.pos + got, (size_t)(nc - got) * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
                  hipStreamSynchronize(stream_) == hipSuccess;
         }
     }
-    if (!ok) {
-        err_ = "corner detection failed";
-        return PVIO_ERR_HIP;
-    }
-    const auto tt1 = std::chrono::steady_clock::now();
-    // the order the atomics handed the slots out in is arbitrary: (response, address) descending makes it canonical again.
-    // One 64-bit key per candidate -- response bits (non-negative floats order like their bit patterns) above the address --
-    // sorts without indirection (an index sort with a two-array comparator took 430 us for 7 300 candidates, this 60).
-    std::vector<uint64_t> &keys = det_keys_;
-    keys.resize((size_t)nc);
-    for (int i = 0; i < nc; ++i) {
+    if (!ok) return fail(PVIO_ERR_HIP, "corner detection failed");
+    *n_all = hs[1];
+    return PVIO_OK;
+}
+
+// The order the atomics handed the slots out in is arbitrary: (response, address) descending makes it canonical again.
+// One 64-bit key per candidate -- response bits (non-negative floats order like their bit patterns) above the address --
+// sorts without indirection (an index sort with a two-array comparator took 430 us for 7 300 candidates, this 60).
+static void order_candidates(const std::vector<float> &val, const std::vector<int> &pos, std::vector<uint64_t> &keys) {
+    keys.resize(val.size());
+    for (size_t i = 0; i < val.size(); ++i) {
         uint32_t bits;
-        std::memcpy(&bits, &val[(size_t)i], 4);
-        keys[(size_t)i] = ((uint64_t)bits << 32) | (uint32_t)pos[(size_t)i];
+        std::memcpy(&bits, &val[i], 4);
+        keys[i] = ((uint64_t)bits << 32) | (uint32_t)pos[i];
     }
     std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
-    const auto tt2 = std::chrono::steady_clock::now();
+}
+
+// The walk of goodFeaturesToTrack over the ordered candidates: a candidate becomes a corner iff no corner accepted before it lies closer than
+// min_distance (min_distance < 1: every candidate), until there are max_corners (> 0) of them.  The number of corners; -1: a grid cell overflowed.
+static int select_corners(const std::vector<uint64_t> &keys, int w, int h, int max_corners, double min_distance, std::vector<int> &grid_cnt, std::vector<float> &grid_xy,
+                          float *xy, float *response) {
+    const int nc = (int)keys.size();
     int n = 0;
     auto key_val = [](uint64_t k) {
         const uint32_t bits = (uint32_t)(k >> 32);
@@ -1055,23 +1032,23 @@ int Klt::detect(const Image *img, int max_corners, double quality, double min_di
         std::memcpy(&f, &bits, 4);
         return f;
     };
-    if (min_distance >= 1) { // greedy minimum-distance selection on a grid (goodFeaturesToTrack)
-        // cell = min_distance: accepted corners are >= min_distance apart, so a cell holds at most four of them (kept five
-        // slots: rounding of the cell size) -- a flat table reused from call to call instead of a vector per cell
-        const int cell = (int)std::lround(min_distance), gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
-        constexpr int kPerCell = 8;
-        det_grid_cnt_.assign((size_t)gw * gh, 0);
-        det_grid_xy_.resize((size_t)gw * gh * kPerCell * 2);
-        const double md2 = min_distance * min_distance;
-        for (int ii = 0; ii < nc; ++ii) {
-            const int p1 = (int)(uint32_t)keys[(size_t)ii];
-            const int y = p1 / w, x = p1 - y * w, xc = x / cell, yc = y / cell;
+    const bool filter = min_distance >= 1; // greedy minimum-distance selection on a grid (goodFeaturesToTrack)
+    // cell = min_distance: accepted corners are >= min_distance apart, so a cell holds at most four of them (kept five
+    // slots: rounding of the cell size) -- a flat table reused from call to call instead of a vector per cell
+    const int cell = filter ? (int)std::lround(min_distance) : 1, gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
+    constexpr int kPerCell = 8;
+    if (filter) grid_cnt.assign((size_t)gw * gh, 0), grid_xy.resize((size_t)gw * gh * kPerCell * 2);
+    const double md2 = min_distance * min_distance;
+    for (int ii = 0; ii < nc; ++ii) {
+        const int p1 = (int)(uint32_t)keys[(size_t)ii];
+        const int y = p1 / w, x = p1 - y * w, xc = x / cell, yc = y / cell;
+        if (filter) {
             bool good = true;
             for (int yy = std::max(0, yc - 1); yy <= std::min(gh - 1, yc + 1) && good; ++yy)
                 for (int xx = std::max(0, xc - 1); xx <= std::min(gw - 1, xc + 1) && good; ++xx) {
                     const size_t c = (size_t)yy * gw + xx;
-                    const float *q = det_grid_xy_.data() + c * kPerCell * 2;
-                    for (int k = 0; k < det_grid_cnt_[c]; ++k) {
+                    const float *q = grid_xy.data() + c * kPerCell * 2;
+                    for (int k = 0; k < grid_cnt[c]; ++k) {
                         const float dx = x - q[2 * k], dy = y - q[2 * k + 1];
                         if (dx * dx + dy * dy < md2) {
                             good = false;
@@ -1081,39 +1058,49 @@ int Klt::detect(const Image *img, int max_corners, double quality, double min_di
                 }
             if (!good) continue;
             const size_t c = (size_t)yc * gw + xc;
-            if (det_grid_cnt_[c] >= kPerCell) { // cannot happen for min_distance >= 1 (see above); refuse rather than overflow
-                err_ = "corner grid cell overflow";
-                return PVIO_ERR_UNSUPPORTED;
-            }
-            det_grid_xy_[(c * kPerCell + det_grid_cnt_[c]) * 2] = (float)x, det_grid_xy_[(c * kPerCell + det_grid_cnt_[c]) * 2 + 1] = (float)y;
-            ++det_grid_cnt_[c];
-            xy[2 * n] = (float)x, xy[2 * n + 1] = (float)y, response[n] = key_val(keys[(size_t)ii]);
-            if (++n >= max_corners && max_corners > 0) break;
+            if (grid_cnt[c] >= kPerCell) return -1; // cannot happen for min_distance >= 1 (see above); refuse rather than overflow
+            grid_xy[(c * kPerCell + grid_cnt[c]) * 2] = (float)x, grid_xy[(c * kPerCell + grid_cnt[c]) * 2 + 1] = (float)y;
+            ++grid_cnt[c];
         }
-    } else {
-        for (int ii = 0; ii < nc; ++ii) {
-            const int p1 = (int)(uint32_t)keys[(size_t)ii];
-            xy[2 * n] = (float)(p1 % w), xy[2 * n + 1] = (float)(p1 / w), response[n] = key_val(keys[(size_t)ii]);
-            if (++n >= max_corners && max_corners > 0) break;
-        }
+        xy[2 * n] = (float)x, xy[2 * n + 1] = (float)y, response[n] = key_val(keys[(size_t)ii]);
+        if (++n >= max_corners && max_corners > 0) break;
     }
+    return n;
+}
+
+int Klt::detect(const Image *img, int max_corners, double quality, double min_distance, float *xy, float *response, int *n_out) {
+    *n_out = 0;
+    (void)hipSetDevice(device_);
+    DetectScratch s(img->w, img->h);
+    void *scratch = d_det_.reserve(s.bytes, s.bytes);
+    if (!scratch) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipMalloc failed");
+    s.bind(scratch);
+    const DetectList list = enqueue_detect(stream_, img, s, quality, min_distance);
+    static const bool timing = getenv("PVIO_KLT_TIMING") != nullptr; // diagnostics: where a detect() call spends its time
+    const auto tt0 = std::chrono::steady_clock::now();
+    std::vector<float> val;
+    std::vector<int> pos;
+    int n_all = 0;
+    if (const int rc = fetch_candidates(s, list, val, pos, &n_all)) return rc;
+    const auto tt1 = std::chrono::steady_clock::now();
+    order_candidates(val, pos, det_keys_);
+    const auto tt2 = std::chrono::steady_clock::now();
+    const int n = select_corners(det_keys_, img->w, img->h, max_corners, min_distance, det_grid_cnt_, det_grid_xy_, xy, response);
+    if (n < 0) return fail(PVIO_ERR_UNSUPPORTED, "corner grid cell overflow");
     *n_out = n;
     if (timing) {
         auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        fprintf(stderr, "[pvio-hip] detect: %d candidates (%d contested) -> %d corners: kernels + copies %.1f us, ordering %.1f us, selection %.1f us\n", hs[1], nc, n, us(tt0, tt1),
-                us(tt1, tt2), us(tt2, std::chrono::steady_clock::now()));
+        fprintf(stderr, "[pvio-hip] detect: %d candidates (%d contested) -> %d corners: kernels + copies %.1f us, ordering %.1f us, selection %.1f us\n", n_all, (int)val.size(), n,
+                us(tt0, tt1), us(tt1, tt2), us(tt2, std::chrono::steady_clock::now()));
     }
     return PVIO_OK;
 }
 
 int Klt::download_response(const Image *img, float *resp) { // tests: the last detect()'s response map
-    const size_t px = (size_t)img->w * img->h;
-    if (!d_det_ || det_cap_ < px * 16) {
-        err_ = "no response map (call detect first)";
-        return PVIO_ERR_INVALID_ARGUMENT;
-    }
-    const float *r = static_cast<const float *>(d_det_) + 3 * px;
-    if (hipMemcpy(resp, r, px * 4, hipMemcpyDeviceToHost) != hipSuccess) return PVIO_ERR_HIP;
+    DetectScratch s(img->w, img->h);
+    if (!d_det_.data() || d_det_.capacity() < s.response_end()) return fail(PVIO_ERR_INVALID_ARGUMENT, "no response map (call detect first)");
+    s.bind(d_det_.data());
+    if (hipMemcpy(resp, s.resp, s.px * 4, hipMemcpyDeviceToHost) != hipSuccess) return PVIO_ERR_HIP;
     return PVIO_OK;
 }
 
@@ -1141,9 +1128,7 @@ struct FundArgs {
 };
 
 __global__ void __launch_bounds__(64) k_fund_hypotheses(FundArgs a) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+    PV_NO_CONTRACT
     const int h = blockIdx.x, lane = threadIdx.x;
     float sp[14], sq[14];
 #pragma unroll
@@ -1167,99 +1152,76 @@ __global__ void __launch_bounds__(64) k_fund_hypotheses(FundArgs a) {
     if (lane < 27) a.models[(size_t)h * 27 + lane] = F[lane];
 }
 
+// The samples of the next `want` hypotheses, in the order the sequential loop would draw them.  Fewer than asked: no admissible sample any
+// more -- the sequential loop stops where it gets there.
+static int draw_batch(pvfm::FmRng &rng, int n, const float *p, const float *q, int want, float *samples) {
+    int drawn = 0;
+    for (; drawn < want; ++drawn) {
+        float *sp = samples + (size_t)drawn * 28, *sq = sp + 14;
+        if (n == 7) std::memcpy(sp, p, 56), std::memcpy(sq, q, 56); // exactly seven points are their own sample
+        else if (!pvfm::fm_draw_sample(rng, n, p, q, sp, sq)) break;
+    }
+    return drawn;
+}
+
+// H hypotheses: their samples go up, counts and models come back; the mask words of ONE model are fetched once the replay knows which (they
+// are 3 nw words per hypothesis: copying them all would be most of the traffic)
+int Klt::evaluate_batch(const FundArgs &a, const FundBlock &b, int H) {
+    char *hb = h_fm_.as<char>(), *db = d_fm_.as<char>();
+    bool ok = hipMemcpyAsync(db + b.samples, hb + b.samples, (size_t)H * 28 * 4, hipMemcpyHostToDevice, stream_) == hipSuccess;
+    hipLaunchKernelGGL(k_fund_hypotheses, dim3(H), dim3(64), 0, stream_, a);
+    ok = ok && hipMemcpyAsync(hb + b.counts, db + b.counts, (b.models - b.counts) + (size_t)H * 27 * 8, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+    ok = ok && hipStreamSynchronize(stream_) == hipSuccess && hipGetLastError() == hipSuccess;
+    if (!ok) return fail(PVIO_ERR_HIP, "fundamental_ransac: batch failed");
+    last_fm_hypotheses_ += H;
+    return PVIO_OK;
+}
+
 int Klt::fundamental_ransac(int n, const float *p, const float *q, double threshold, double confidence, int max_iterations, uint8_t *mask, double *F_out, int *n_inliers) {
-    constexpr int kModel = 7;
     *n_inliers = 0;
     for (int i = 0; i < n; ++i) mask[i] = 0;
     last_fm_hypotheses_ = 0;
-    if (n < kModel) return PVIO_OK;
+    if (n < 7) return PVIO_OK;
     (void)hipSetDevice(device_);
-    const int nw = (n + 63) / 64;
     const int cap_h = std::max(1, std::min(max_iterations, 1000));
-    // one device block + its pinned mirror: [p | q | samples | counts | models | masks]
-    const size_t off_q = (size_t)n * 8, off_s = off_q + (size_t)n * 8, off_c = (off_s + (size_t)cap_h * 28 * 4 + 15) & ~(size_t)15,
-                 off_m = off_c + (size_t)cap_h * 16, off_k = off_m + (size_t)cap_h * 27 * 8, total = off_k + (size_t)cap_h * 3 * nw * 8;
-    if (total > fm_cap_) {
-        if (d_fm_) (void)hipFree(d_fm_);
-        if (h_fm_) (void)hipHostFree(h_fm_);
-        d_fm_ = h_fm_ = nullptr, fm_cap_ = 0;
-        if (hipMalloc(&d_fm_, total) != hipSuccess || hipHostMalloc(&h_fm_, total) != hipSuccess) {
-            err_ = "fundamental_ransac: allocation failed";
-            return PVIO_ERR_OUT_OF_MEMORY;
-        }
-        fm_cap_ = total;
-    }
-    char *hb = static_cast<char *>(h_fm_), *db = static_cast<char *>(d_fm_);
-    std::memcpy(hb, p, (size_t)n * 8), std::memcpy(hb + off_q, q, (size_t)n * 8);
-    if (hipMemcpyAsync(db, hb, off_s, hipMemcpyHostToDevice, stream_) != hipSuccess) {
-        err_ = "fundamental_ransac: upload failed";
-        return PVIO_ERR_HIP;
-    }
+    const FundBlock b(n, cap_h);
+    if (!(d_fm_.reserve(b.bytes, b.bytes) && h_fm_.reserve(b.bytes, b.bytes))) return fail(PVIO_ERR_OUT_OF_MEMORY, "fundamental_ransac: allocation failed");
+    char *hb = h_fm_.as<char>(), *db = d_fm_.as<char>();
+    std::memcpy(hb + b.p, p, (size_t)n * 8), std::memcpy(hb + b.q, q, (size_t)n * 8);
+    if (hipMemcpyAsync(db + b.p, hb + b.p, b.samples - b.p, hipMemcpyHostToDevice, stream_) != hipSuccess) return fail(PVIO_ERR_HIP, "fundamental_ransac: upload failed");
+    FundArgs a;
+    a.n = n, a.nw = b.nw, a.p = reinterpret_cast<const float *>(db + b.p), a.q = reinterpret_cast<const float *>(db + b.q);
+    a.samples = reinterpret_cast<const float *>(db + b.samples), a.thr2 = threshold * threshold;
+    a.counts = reinterpret_cast<int *>(db + b.counts), a.models = reinterpret_cast<double *>(db + b.models), a.masks = reinterpret_cast<unsigned long long *>(db + b.masks);
+    const int *cnt = reinterpret_cast<const int *>(hb + b.counts);
+    const double *models = reinterpret_cast<const double *>(hb + b.models);
     pvfm::FmRng rng((uint64_t)-1);
-    int niters = n == kModel ? 1 : max_iterations, iter = 0, max_good = 0;
-    double bestF[9] = {0};
-    std::vector<unsigned long long> best_words((size_t)nw, 0);
-    float *hs = reinterpret_cast<float *>(hb + off_s);
-    int batch = 48;
+    pvfm::FmBest run(n, max_iterations);
+    std::vector<unsigned long long> best_words((size_t)b.nw, 0);
+    int iter = 0, batch = 48;
     bool exhausted = false;
-    while (iter < niters && !exhausted) {
-        int H = std::min(std::min(batch, niters - iter), cap_h);
+    while (iter < run.niters && !exhausted) {
+        const int want = std::min(std::min(batch, run.niters - iter), cap_h);
         batch = batch == 48 ? 192 : cap_h;
-        int drawn = 0;
-        for (; drawn < H; ++drawn) {
-            float *sp = hs + (size_t)drawn * 28, *sq = sp + 14;
-            if (n > kModel) {
-                if (!pvfm::fm_draw_sample(rng, n, p, q, sp, sq)) {
-                    exhausted = true; // no admissible sample any more: the sequential loop stops where it gets here
-                    break;
-                }
-            } else {
-                std::memcpy(sp, p, 56), std::memcpy(sq, q, 56);
-            }
-        }
-        H = drawn;
+        const int H = draw_batch(rng, n, p, q, want, reinterpret_cast<float *>(hb + b.samples));
+        exhausted = H < want;
         if (H == 0) break;
-        FundArgs a;
-        a.n = n, a.nw = nw, a.p = reinterpret_cast<const float *>(db), a.q = reinterpret_cast<const float *>(db + off_q);
-        a.samples = reinterpret_cast<const float *>(db + off_s), a.thr2 = threshold * threshold;
-        a.counts = reinterpret_cast<int *>(db + off_c), a.models = reinterpret_cast<double *>(db + off_m), a.masks = reinterpret_cast<unsigned long long *>(db + off_k);
-        bool ok = hipMemcpyAsync(db + off_s, hb + off_s, (size_t)H * 28 * 4, hipMemcpyHostToDevice, stream_) == hipSuccess;
-        hipLaunchKernelGGL(k_fund_hypotheses, dim3(H), dim3(64), 0, stream_, a);
-        // counts and models come back now; the mask words of ONE model are fetched once the replay knows which (they are 3 nw words per
-        // hypothesis: copying them all would be most of the traffic)
-        ok = ok && hipMemcpyAsync(hb + off_c, db + off_c, (off_m - off_c) + (size_t)H * 27 * 8, hipMemcpyDeviceToHost, stream_) == hipSuccess;
-        ok = ok && hipStreamSynchronize(stream_) == hipSuccess && hipGetLastError() == hipSuccess;
-        if (!ok) {
-            err_ = "fundamental_ransac: batch failed";
-            return PVIO_ERR_HIP;
-        }
-        last_fm_hypotheses_ += H;
-        const int *cnt = reinterpret_cast<const int *>(hb + off_c);
-        const double *models = reinterpret_cast<const double *>(hb + off_m);
+        if (const int rc = evaluate_batch(a, b, H)) return rc;
+        // the sequential loop's bookkeeping over the counts, in the order the samples were drawn; hypotheses beyond its end are not looked at
         int win_h = -1, win_m = -1;
-        for (int hh = 0; hh < H && iter < niters; ++hh, ++iter) {
-            const int nm = cnt[4 * hh];
-            for (int m = 0; m < nm; ++m) {
-                const int good = cnt[4 * hh + 1 + m];
-                if (good > std::max(max_good, kModel - 1)) {
-                    win_h = hh, win_m = m, max_good = good;
-                    std::memcpy(bestF, models + (size_t)hh * 27 + 9 * m, sizeof bestF);
-                    niters = pvfm::fm_update_iterations(confidence, (double)(n - good) / n, kModel, niters);
-                }
-            }
-        }
+        for (int hh = 0; hh < H && iter < run.niters; ++hh, ++iter)
+            for (int m = 0; m < cnt[4 * hh]; ++m)
+                if (run.offer(cnt[4 * hh + 1 + m], models + (size_t)hh * 27 + 9 * m, n, confidence)) win_h = hh, win_m = m;
         if (win_h >= 0) { // the best model of the run so far lives in this batch: its mask words
-            if (hipMemcpy(best_words.data(), a.masks + ((size_t)win_h * 3 + win_m) * nw, (size_t)nw * 8, hipMemcpyDeviceToHost) != hipSuccess) {
-                err_ = "fundamental_ransac: mask download failed";
-                return PVIO_ERR_HIP;
-            }
+            if (hipMemcpy(best_words.data(), a.masks + ((size_t)win_h * 3 + win_m) * b.nw, (size_t)b.nw * 8, hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(PVIO_ERR_HIP, "fundamental_ransac: mask download failed");
         }
     }
-    if (max_good > 0) {
+    if (run.max_good > 0) {
         for (int i = 0; i < n; ++i) mask[i] = (uint8_t)((best_words[(size_t)i >> 6] >> (i & 63)) & 1ull);
-        if (F_out) std::memcpy(F_out, bestF, sizeof bestF);
+        if (F_out) std::memcpy(F_out, run.bestF, sizeof run.bestF);
     }
-    *n_inliers = max_good;
+    *n_inliers = run.max_good;
     return PVIO_OK;
 }
 

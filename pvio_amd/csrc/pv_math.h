@@ -16,6 +16,14 @@
 #define PV_HD inline
 #endif
 
+// First statement of a function body whose float operations must not be contracted into FMAs (hipcc contracts by default).  Scoped to the body, so
+// that including a header does not change how the rest of a translation unit is compiled; g++ builds say -ffp-contract=off (or push the option).
+#if defined(__clang__)
+#define PV_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define PV_NO_CONTRACT
+#endif
+
 namespace pv {
 
 PV_HD void v3_set(double *o, double a, double b, double c) { o[0] = a, o[1] = b, o[2] = c; }
@@ -84,9 +92,7 @@ PV_HD void m3_inverse(double *o, const double *m) { // adjugate / determinant (E
 // reference's first-time gauge prior multiplies this error by 1e15 (sliding_window_tracker.cpp:105-111), which
 // would turn 1-ulp contraction noise into O(1e-3) of cost.
 PV_HD void q_mul(double *o, const double *a, const double *b) { // o must not alias
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+    PV_NO_CONTRACT
     o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
     o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
     o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];

@@ -38,11 +38,9 @@ int find_fundamental_ransac(int n, const float *p, const float *q, double thresh
     pvfm::FmRng rng((uint64_t)-1);
     const double thr2 = threshold * threshold;
     std::vector<uint8_t> cur((size_t)n), best((size_t)n, 0);
-    int niters = max_iterations, max_good = 0;
-    double bestF[9] = {0};
+    pvfm::FmBest run(n, max_iterations);
     float sp[14], sq[14];
-    if (n == kModel) niters = 1;
-    for (int iter = 0; iter < niters; ++iter) {
+    for (int iter = 0; iter < run.niters; ++iter) {
         if (n > kModel) {
             if (!pvfm::fm_draw_sample(rng, n, p, q, sp, sq)) {
                 if (iter == 0) return 0;
@@ -54,20 +52,15 @@ int find_fundamental_ransac(int n, const float *p, const float *q, double thresh
         double F[27];
         const int nm = pvfm::fm_seven_point(sp, sq, F);
         for (int m = 0; m < nm; ++m) {
-            const int good = count_inliers(n, p, q, F + 9 * m, thr2, cur, std::max(max_good, kModel - 1));
-            if (good > std::max(max_good, kModel - 1)) {
-                std::swap(cur, best);
-                std::copy(F + 9 * m, F + 9 * m + 9, bestF);
-                max_good = good;
-                niters = pvfm::fm_update_iterations(confidence, (double)(n - good) / n, kModel, niters);
-            }
+            const int good = count_inliers(n, p, q, F + 9 * m, thr2, cur, run.to_beat());
+            if (run.offer(good, F + 9 * m, n, confidence)) std::swap(cur, best);
         }
     }
-    if (max_good > 0) {
+    if (run.max_good > 0) {
         mask = best;
-        if (F_out) std::copy(bestF, bestF + 9, F_out);
+        if (F_out) std::copy(run.bestF, run.bestF + 9, F_out);
     }
-    return max_good;
+    return run.max_good;
 }
 
 } // namespace pvio
