@@ -257,6 +257,40 @@ int32_t pvio_hip_ba_last_candidate_repeats(const pvio_hip_ctx *ctx);
  * an upload, contexts created with use_graph = 0, a landmark shard whose capture failed) */
 int32_t pvio_hip_ba_graph_replays(const pvio_hip_ctx *ctx);
 
+/* Marginal covariances of the window at `state`.  NO REFERENCE COUNTERPART: BundleAdjustor returns states and nothing about how well
+ * they are determined.
+ *   linearization   the solver's own iteration 0 at `state`: CauchyLoss(1) reweighting of reprojection and plane factors, lm_multiplicity,
+ *                   FF_FIX_POSE blocks constant, live biases from `state`, IMU factors only with use_inertial, prior and rotation priors
+ *                   as the solver sees them; no Jacobi scaling, no damping
+ *   S               H_pp - sum_l W_l^T W_l / H_ll (H = J^T J in tangent coordinates), over the landmarks with a factor and a finite H_ll > 0
+ *   coordinates     15 f + k (error-state order), for vision-only windows too.  A coordinate is free unless its block is constant or not
+ *                   in the problem (a fixed pose; velocity and biases of a window without IMU factors and prior) or its row of S is exactly
+ *                   zero (velocity / biases of a frame no IMU factor or prior reaches).  Every output has zero rows and columns elsewhere.
+ *   pivot rule      S over the free coordinates is scaled to unit diagonal, c_i = 1 / sqrt(S_ii), and factored by Cholesky in coordinate
+ *                   order.  A pivot <= PVIO_COV_MIN_PIVOT means the window is unobservable: positive_definite = 0, first_bad_coord is
+ *                   set, NO other output is written and the call still returns PVIO_OK.  (Singular windows -- a vision-only window with
+ *                   one fixed frame, a VIO window without a prior -- have smallest pivots within 5e-14 of zero; the worst legitimate
+ *                   window, the 1e15 gauge prior, has 1.5e-6.)
+ *   outputs         Sigma = C S^-1 C;  lm_var[l] = 1 / H_ll + W_l Sigma W_l^T / H_ll^2, +inf for a landmark without factors or without
+ *                   a finite positive H_ll
+ * Every output array is caller-allocated.  Two calls on the same input return the same bits.  Landmark-sharded contexts
+ * (world_size > 1, debug_force_sharded) return PVIO_ERR_UNSUPPORTED.  Like pvio_hip_ba_marginalize, the call leaves no uploaded window
+ * behind: pvio_hip_ba_solve_resident needs a new pvio_hip_ba_upload. */
+#define PVIO_COV_MIN_PIVOT 1e-10
+typedef struct pvio_ba_covariance {
+    int32_t positive_definite;  /* out */
+    int32_t first_bad_coord;    /* out: 15*f+k of the failing pivot, else -1 */
+    double *frame_cov;          /* [N][15][15] marginal covariance of each frame's tangent */
+    double *joint_cov;          /* optional [15N][15N] */
+    double *lm_var;             /* optional [M] */
+    uint8_t *coord_free;        /* optional [15N] */
+} pvio_ba_covariance;
+int32_t pvio_hip_ba_covariance(pvio_hip_ctx *ctx, const pvio_ba_problem *problem,
+                               const pvio_ba_state *state, pvio_ba_covariance *out);
+/* diagnostics: hipEvent time in ms of k_cov_assemble, k_cov_invert and k_cov_landmarks in the last pvio_hip_ba_covariance of this context;
+ * recorded only when PVIO_HIP_TIMING is set in the environment (zeros otherwise) */
+int32_t pvio_hip_ba_covariance_kernel_ms(const pvio_hip_ctx *ctx, double ms[3]);
+
 /* multi-GPU (landmark shards, one process per GPU): RCCL communicator bootstrap.
  * rank 0 creates the 128-byte unique id, the launcher broadcasts it (torch.distributed), every rank inits. */
 int32_t pvio_hip_comm_unique_id(uint8_t id[128]);

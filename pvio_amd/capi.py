@@ -70,6 +70,14 @@ class BAPriorC(C.Structure):
                 ("info_matrix", c_double_p), ("info_vector", c_double_p)]
 
 
+class BACovarianceC(C.Structure):
+    _fields_ = [("positive_definite", C.c_int32), ("first_bad_coord", C.c_int32), ("frame_cov", c_double_p), ("joint_cov", c_double_p),
+                ("lm_var", c_double_p), ("coord_free", c_uint8_p)]
+
+
+COV_MIN_PIVOT = 1e-10  # PVIO_COV_MIN_PIVOT
+
+
 class BAKernelTimesC(C.Structure):
     _fields_ = [("total_ms", C.c_double * 4), ("launches", C.c_int32 * 4), ("phase_ticks", (C.c_int64 * 32) * 4),
                 ("comm_ms", C.c_double * 2), ("comm_launches", C.c_int32 * 2)]
@@ -85,7 +93,7 @@ ABI_VERSION = 2  # PVIO_HIP_ABI_VERSION of include/pvio_hip.h these ctypes struc
 # every symbol include/pvio_hip.h declares (tests check the .so exports all of them)
 EXPORTS = [
     "pvio_hip_create", "pvio_hip_destroy", "pvio_hip_last_error", "pvio_hip_version", "pvio_hip_abi_version",
-    "pvio_hip_ba_solve", "pvio_hip_ba_marginalize", "pvio_hip_ba_reprojection_error",
+    "pvio_hip_ba_solve", "pvio_hip_ba_marginalize", "pvio_hip_ba_reprojection_error", "pvio_hip_ba_covariance", "pvio_hip_ba_covariance_kernel_ms",
     "pvio_hip_ba_upload", "pvio_hip_ba_solve_resident", "pvio_hip_ba_download", "pvio_hip_ba_profile_resident", "pvio_hip_ba_last_candidate_repeats", "pvio_hip_ba_graph_replays",
     "pvio_hip_comm_unique_id", "pvio_hip_comm_init", "pvio_preintegrate",
     "pvio_hip_image_create", "pvio_hip_image_release", "pvio_hip_image_download_level", "pvio_hip_klt_track", "pvio_hip_image_detect", "pvio_hip_image_download_response",
@@ -124,6 +132,10 @@ def load(path=None):
     lib.pvio_hip_ba_solve.restype = C.c_int32
     lib.pvio_hip_ba_marginalize.argtypes = [vp, C.POINTER(BAProblemC), C.POINTER(BAStateC), C.c_int32, C.POINTER(BAPriorC)]
     lib.pvio_hip_ba_marginalize.restype = C.c_int32
+    lib.pvio_hip_ba_covariance.argtypes = [vp, C.POINTER(BAProblemC), C.POINTER(BAStateC), C.POINTER(BACovarianceC)]
+    lib.pvio_hip_ba_covariance.restype = C.c_int32
+    lib.pvio_hip_ba_covariance_kernel_ms.argtypes = [vp, c_double_p]
+    lib.pvio_hip_ba_covariance_kernel_ms.restype = C.c_int32
     lib.pvio_hip_ba_reprojection_error.argtypes = [vp, C.POINTER(BAProblemC), C.POINTER(BAStateC), c_double_p]
     lib.pvio_hip_ba_reprojection_error.restype = C.c_int32
     lib.pvio_hip_ba_upload.argtypes = [vp, C.POINTER(BAProblemC), C.POINTER(BAStateC)]

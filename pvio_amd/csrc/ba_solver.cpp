@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "ba_cov.h"
 #include "ba_kernels.h"
 #include "sym_eig.h"
 #include <cmath>
@@ -67,6 +68,8 @@ BASolver::~BASolver() {
     invalidate_graph();
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
+    for (hipEvent_t ev : cov_ev_)
+        if (ev) (void)hipEventDestroy(ev);
     if (stream_) (void)hipStreamDestroy(stream_);
 }
 int BASolver::fail(int code, const std::string &msg) {
@@ -1254,4 +1257,86 @@ int BASolver::marginalize(const pvio_ba_problem *pb, const pvio_ba_state *st, in
     return PVIO_OK;
 }
 
+// Marginal covariances of the window at `st` (pvio_hip_ba_covariance; no reference counterpart).  The first half is marginalize()'s -- upload, reset,
+// one undamped linearization, the reduction -- in MODE_INIT over the whole window: the robustified, multiplicity-weighted J^T J the solver's own
+// iteration 0 sees, constant blocks constant.  The kernels of ba_cov.hip then assemble, scale, invert and scatter on the solver's stream; the
+// results come back as ONE copy through a pinned buffer.
+int BASolver::covariance(const pvio_ba_problem *pb, const pvio_ba_state *st, pvio_ba_covariance *out) {
+    if (!pb || !st || !out || !out->frame_cov) return fail(PVIO_ERR_INVALID_ARGUMENT, "null argument");
+    if (sharded_) return fail(PVIO_ERR_UNSUPPORTED, "pvio_hip_ba_covariance: landmark-sharded contexts are not supported");
+    static const bool timing = std::getenv("PVIO_HIP_TIMING") != nullptr; // diagnostics: hipEvents around the three kernels
+    int rc = upload(pb, st, /*may_return_early=*/true); // (this call synchronizes below, before the caller's arrays can change)
+    if (rc != PVIO_OK) return rc;
+    const Dims &dm = v_.dm;
+    const size_t N = (size_t)dm.N, M = (size_t)dm.M, D = 15 * N;
+    if (check(launch_reset(v_, fs_init_, rho_init_, v_.ctrl, stream_), "k_reset")) return PVIO_ERR_HIP;
+    std::memset(h_ctrl_, 0, sizeof(Ctrl));
+    h_ctrl_->mode = MODE_INIT;
+    h_ctrl_->mu = 0.0; // no damping: the Schur weight of a landmark is 1 / H_ll
+    if (check(hipMemcpyAsync(v_.ctrl, h_ctrl_, sizeof(Ctrl), hipMemcpyHostToDevice, stream_), "ctrl")) return PVIO_ERR_HIP;
+    hipError_t e;
+    if ((e = launch_linearize(v_, stream_)) != hipSuccess) return check(e, "k_linearize");
+    if ((e = launch_reduce(v_, stream_, 0)) != hipSuccess) return check(e, "k_reduce");
+
+    // every coordinate that can be free: the pose of a frame that is not fixed, the motion blocks of a 15-dimensional system
+    size_t max_coords = 0;
+    for (size_t f = 0; f < N; ++f) max_coords += (pb->frame_fixed[f] ? 0 : 6) + (dm.d == 15 ? 9 : 0);
+    // results: header | coord_free | frame_cov | lm_var | joint_cov (last: copied back only when the caller wants it)
+    const size_t o_free = 2, o_frame = o_free + (D + 7) / 8, o_lm = o_frame + N * 225, o_joint = o_lm + ((M + 7) & ~(size_t)7), n_res = o_joint + D * D;
+    // work: S | scale | tiles | sig6 | row_nz, free_coord (int32)
+    const size_t w_scale = D * D, w_tiles = w_scale + D, w_sig6 = w_tiles + cov_tile_doubles(max_coords), w_int = w_sig6 + 36 * N * N, n_work = w_int + D;
+    double *d_res = nullptr, *d_work = nullptr;
+    {
+        bool grew = false;
+        if (!dev(pool_, "cov_result", n_res, &d_res, &grew) || !dev(pool_, "cov_work", n_work, &d_work, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "covariance buffers");
+    }
+    const size_t n_back = out->joint_cov ? n_res : o_joint;
+    double *const h_back = static_cast<double *>(h_cov_.reserve(n_back * sizeof(double), (n_back + n_back / 2) * sizeof(double)));
+    if (!h_back) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+    CovArgs a{};
+    a.D = (int32_t)D, a.max_coords = (int32_t)max_coords;
+    a.Sfull = d_work, a.scale = d_work + w_scale, a.tiles = d_work + w_tiles, a.sig6 = d_work + w_sig6;
+    a.row_nz = reinterpret_cast<int32_t *>(d_work + w_int), a.free_coord = a.row_nz + D;
+    a.hdr = reinterpret_cast<CovHdr *>(d_res), a.coord_free = reinterpret_cast<uint8_t *>(d_res + o_free);
+    a.frame_cov = d_res + o_frame, a.lm_var = d_res + o_lm, a.joint_cov = d_res + o_joint;
+    // coordinates that are not free have zero rows and columns in every output: the kernels write the free part only
+    if (check(hipMemsetAsync(d_res, 0, n_res * sizeof(double), stream_), "memset")) return PVIO_ERR_HIP;
+    if (check(hipMemsetAsync(a.sig6, 0, 36 * N * N * sizeof(double), stream_), "memset")) return PVIO_ERR_HIP;
+    if (timing)
+        for (hipEvent_t &ev : cov_ev_)
+            if (!ev && check(hipEventCreate(&ev), "hipEventCreate")) return PVIO_ERR_HIP;
+    if (timing) (void)hipEventRecord(cov_ev_[0], stream_);
+    if ((e = launch_cov_assemble(v_, a, stream_)) != hipSuccess) return check(e, "k_cov_assemble");
+    if (timing) (void)hipEventRecord(cov_ev_[1], stream_);
+    if ((e = launch_cov_invert(v_, a, stream_)) != hipSuccess) return check(e, "k_cov_invert");
+    if (timing) (void)hipEventRecord(cov_ev_[2], stream_);
+    if (out->lm_var && (e = launch_cov_landmarks(v_, a, stream_)) != hipSuccess) return check(e, "k_cov_landmarks");
+    if (timing) (void)hipEventRecord(cov_ev_[3], stream_);
+    if (check(hipMemcpyAsync(h_back, d_res, n_back * sizeof(double), hipMemcpyDeviceToHost, stream_), "D2H")) return PVIO_ERR_HIP;
+    if (check(hipStreamSynchronize(stream_), "covariance sync")) return PVIO_ERR_HIP;
+    stage_in_flight_ = false;
+    uploaded_ = false; // the device buffers now hold an undamped linearization, not a solvable window
+    if (timing)
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0.0f;
+            (void)hipEventElapsedTime(&ms, cov_ev_[k], cov_ev_[k + 1]);
+            cov_ms_[k] = ms;
+        }
+    const CovHdr *hdr = reinterpret_cast<const CovHdr *>(h_back);
+    if (hdr->layout_error) return fail(PVIO_ERR_HIP, "k_cov_assemble: unexpected order of the tile tasks");
+    out->positive_definite = hdr->positive_definite;
+    out->first_bad_coord = hdr->positive_definite ? -1 : hdr->first_bad_coord;
+    if (!hdr->positive_definite) return PVIO_OK; // an unobservable window is an answer, not an error: nothing else is written
+    std::memcpy(out->frame_cov, h_back + o_frame, N * 225 * sizeof(double));
+    if (out->joint_cov) std::memcpy(out->joint_cov, h_back + o_joint, D * D * sizeof(double));
+    if (out->lm_var) std::memcpy(out->lm_var, h_back + o_lm, M * sizeof(double));
+    if (out->coord_free) std::memcpy(out->coord_free, h_back + o_free, D);
+    return PVIO_OK;
+}
+
 } // namespace pvba
+
+// The kernels of covariance() and their launchers.  They are compiled as part of this translation unit, not as an object of their own: whatever
+// builds ba_solver.cpp -- the product Makefile, the fiber emulator of tests/hipemu, the variant builds of tests/micro -- has them without a
+// change to its list of sources.
+#include "ba_cov.hip"

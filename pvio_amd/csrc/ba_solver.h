@@ -54,6 +54,8 @@ class BASolver {
     int download(pvio_ba_state *st);                                   // D2H of the accepted iterate (+ quality pass)
     int reprojection_error(double *out);
     int marginalize(const pvio_ba_problem *pb, const pvio_ba_state *st, int victim, pvio_ba_prior *out);
+    int covariance(const pvio_ba_problem *pb, const pvio_ba_state *st, pvio_ba_covariance *out); // marginal covariances of the window (ba_cov.hip)
+    const double *last_covariance_kernel_ms() const { return cov_ms_; } // k_cov_assemble, k_cov_invert, k_cov_landmarks of the last call (PVIO_HIP_TIMING)
     void set_comm(Comm *c) { comm_ = c; }
     const std::string &error() const { return err_; }
     hipStream_t stream() const { return stream_; }
@@ -91,6 +93,9 @@ class BASolver {
     bool stage_in_flight_ = false; // upload(may_return_early) left its staged copy queued; cleared by the next stream synchronization
     pvhip::PinnedBuffer h_back_; // pinned read-back of one marginalization pass (doubles)
     std::vector<double> marg_H_, marg_C_, marg_V_; // host work arrays of a marginalization (15N x 15N, twice 15(N-1) x 15(N-1))
+    pvhip::PinnedBuffer h_cov_;  // pinned read-back of one covariance call
+    hipEvent_t cov_ev_[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three kernels of a covariance call, created on first use (PVIO_HIP_TIMING)
+    double cov_ms_[3] = {0.0, 0.0, 0.0};
     pvhip::PinnedBuffer h_pack_; // pinned: a solve's packed results (k_quality `pack`, doubles)
     const double *fs_init_ = nullptr, *rho_init_ = nullptr; // initial state inside the inputs slab
     Ctrl h_ctrl_tmpl_{};                                    // what a solve's control block starts from (k_reset copies the device copy)

@@ -100,6 +100,15 @@ int32_t pvio_hip_ba_marginalize(pvio_hip_ctx *ctx, const pvio_ba_problem *proble
     if (!ctx || !problem || !state || !out) return PVIO_ERR_INVALID_ARGUMENT;
     return ctx->ba->marginalize(problem, state, victim, out);
 }
+int32_t pvio_hip_ba_covariance(pvio_hip_ctx *ctx, const pvio_ba_problem *problem, const pvio_ba_state *state, pvio_ba_covariance *out) {
+    if (!ctx || !problem || !state || !out || !out->frame_cov) return PVIO_ERR_INVALID_ARGUMENT;
+    return ctx->ba->covariance(problem, state, out);
+}
+int32_t pvio_hip_ba_covariance_kernel_ms(const pvio_hip_ctx *ctx, double ms[3]) {
+    if (!ctx || !ctx->ba || !ms) return PVIO_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < 3; ++k) ms[k] = ctx->ba->last_covariance_kernel_ms()[k];
+    return PVIO_OK;
+}
 int32_t pvio_hip_ba_reprojection_error(pvio_hip_ctx *ctx, const pvio_ba_problem *problem, const pvio_ba_state *state, double *mean_pixel_error) {
     if (!ctx || !problem || !state || !mean_pixel_error) return PVIO_ERR_INVALID_ARGUMENT;
     int rc = ctx->ba->upload(problem, state);

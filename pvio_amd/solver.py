@@ -109,6 +109,36 @@ class HipContext:
         self._check(self.lib.pvio_hip_ba_marginalize(self.ctx, C.byref(pb), C.byref(st), int(victim), C.byref(pr)), "pvio_hip_ba_marginalize")
         return S, s, IM, iv
 
+    def covariance(self, problem, state, joint=False, landmarks=False, into=None):
+        """pvio_hip_ba_covariance: marginal covariances of the window at `state` (include/pvio_hip.h).  Returns a dict: positive_definite,
+        first_bad_coord, frame_cov [N, 15, 15], coord_free [15 N] and, on request, joint_cov [15 N, 15 N] and lm_var [M].  `into`: arrays of
+        those names to be written in place of fresh ones (an unobservable window leaves them as they are)."""
+        pb, st = problem.as_c(), state.as_c()
+        N, M = problem.n_frames, problem.n_landmarks
+        into = into or {}
+        res = dict(frame_cov=into.get("frame_cov", np.zeros((N, 15, 15))), coord_free=into.get("coord_free", np.zeros(15 * N, np.uint8)))
+        if joint:
+            res["joint_cov"] = into.get("joint_cov", np.zeros((15 * N, 15 * N)))
+        if landmarks:
+            res["lm_var"] = into.get("lm_var", np.zeros(max(M, 1))[:M])
+        cv = capi.BACovarianceC()
+        cv.positive_definite, cv.first_bad_coord = -1, -1
+        cv.frame_cov = res["frame_cov"].ctypes.data_as(capi.c_double_p)
+        cv.coord_free = res["coord_free"].ctypes.data_as(capi.c_uint8_p)
+        if joint:
+            cv.joint_cov = res["joint_cov"].ctypes.data_as(capi.c_double_p)
+        if landmarks:
+            cv.lm_var = res["lm_var"].ctypes.data_as(capi.c_double_p)
+        self._check(self.lib.pvio_hip_ba_covariance(self.ctx, C.byref(pb), C.byref(st), C.byref(cv)), "pvio_hip_ba_covariance")
+        res["positive_definite"], res["first_bad_coord"] = int(cv.positive_definite), int(cv.first_bad_coord)
+        return res
+
+    def covariance_kernel_ms(self):
+        """hipEvent ms of k_cov_assemble, k_cov_invert, k_cov_landmarks in the last covariance() (recorded only with PVIO_HIP_TIMING set)"""
+        ms = np.zeros(3)
+        self._check(self.lib.pvio_hip_ba_covariance_kernel_ms(self.ctx, ms.ctypes.data_as(capi.c_double_p)), "pvio_hip_ba_covariance_kernel_ms")
+        return ms
+
 
 class HipUndistort:
     """Device-resident fixed-point remap tables (pvio_hip_undistort_create): map_xy int16 [h][w][2], map_frac uint16 [h][w]."""
