@@ -4,6 +4,10 @@
 // (pvio/src/pvio/estimation/bundle_adjustor.cpp:63-299): the flat problem is uploaded once, the whole
 // trust-region loop runs on the device (kernels in ba_kernels.hip), the host only replays a graph of
 // "slots" (linearize -> reduce -> dense -> backsub) until the device-side state machine reports done.
+//
+// In order: upload in its five steps; the read-back layouts (SolvePack, MargGather, CovSlabs); solve in its steps (enqueue_slot, run_slots,
+// request_solve_buffers, reset_for_solve, ProfileScope, profiled_slot, time_limit_reached, fill_summary, unpack_results); the one-shot calls
+// marginalize and covariance above linearize_once.  The marginalization's dense host algebra is marg_prior.h.
 #include "ba_solver.h"
 
 #include <algorithm>
@@ -13,8 +17,7 @@
 
 #include "ba_cov.h"
 #include "ba_kernels.h"
-#include "sym_eig.h"
-#include <cmath>
+#include "marg_prior.h"
 
 namespace pvba {
 constexpr bool kDenseLookAheadDefault = true; // same-box A/B (profiles/r3_ab_lookahead.txt): 12 076 -> 12 678 iterations/s
@@ -196,6 +199,24 @@ static const UploadSwitches &upload_switches() {
     }();
     return sw;
 }
+
+// Diagnostic and test switches of the calls behind an upload.  Read once per process, at the first call that asks.
+struct SolverSwitches {
+    bool debug_ctrl;    // PVIO_HIP_DEBUG_CTRL=1 (plain launches only): the control block as each kernel of a slot leaves it (dump_ctrl)
+    bool sharded_graph; // PVIO_HIP_SHARDED_GRAPH=0 turns the capture of landmark-sharded slots off (run_slots)
+    bool timing;        // PVIO_HIP_TIMING=1: where the host's time of a solve and of a marginalization goes; hipEvents around the kernels of a covariance call
+    int timeout_rank;   // PVIO_HIP_DEBUG_TIMEOUT_RANK, tests: only this rank sees its clock run out (the ranks must still leave in the same round); -1: not set
+};
+static const SolverSwitches &solver_switches() {
+    static const SolverSwitches sw = [] {
+        const char *sg = std::getenv("PVIO_HIP_SHARDED_GRAPH"), *tr = std::getenv("PVIO_HIP_DEBUG_TIMEOUT_RANK");
+        return SolverSwitches{std::getenv("PVIO_HIP_DEBUG_CTRL") != nullptr, !(sg != nullptr && std::atoi(sg) == 0), std::getenv("PVIO_HIP_TIMING") != nullptr, tr ? std::atoi(tr) : -1};
+    }();
+    return sw;
+}
+
+using Clock = std::chrono::steady_clock;
+static double us(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
 
 // Everything an upload derives on the host.  Owns the derived arrays until the DMA has left: staging sends the large ones from where they lie.
 struct UploadPlan {
@@ -653,6 +674,80 @@ int BASolver::upload(const pvio_ba_problem *pb, const pvio_ba_state *st, bool ma
     return commit(pb, work, may_return_early);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Read-back layouts, each written once (in doubles): the device request, the pinned reservation, the kernel arguments
+// and the host-side pointers all come from them.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// a solve's packed results (k_quality `pack`): frame states | inverse depths | quality | valid bytes, in one pinned buffer
+struct SolvePack {
+    size_t M, o_rho, o_quality, o_valid, n;
+    explicit SolvePack(const Dims &dm) : M((size_t)dm.M), o_rho((size_t)dm.N * 16), o_quality(o_rho + M), o_valid(o_rho + 2 * M), n(o_valid + (M + 7) / 8) {}
+};
+
+// the eight arrays a marginalization reads back, gathered on the device (k_gather) into one block: segment k starts at off[k], a multiple of 8
+struct MargGather {
+    size_t n[8], off[9];
+    explicit MargGather(const Dims &dm) {
+        const size_t Ns = dm.N, Dp = 15 * (size_t)dm.prior_n, nS = (size_t)dm.n_tasks * 9, nV = (size_t)kNumPoseVec * dm.P6;
+        const size_t sizes[8] = {nS + nV + kNumLinScal, Ns * 900, Ns * 30, Dp * Dp, Dp, Ns * 9, Ns * 3, ((size_t)dm.n_tasks + 1) / 2};
+        off[0] = 0;
+        for (int k = 0; k < 8; ++k) n[k] = sizes[k], off[k + 1] = off[k] + ((n[k] + 7) & ~(size_t)7);
+    }
+    size_t total() const { return off[8]; }
+    GatherArgs args(const View &v) const {
+        const void *src[8] = {v.red, v.pre_H, v.pre_g, v.prior_H, v.prior_g, v.rot_H, v.rot_g, v.task_desc};
+        GatherArgs ga;
+        for (int k = 0; k < 8; ++k) {
+            ga.src[k] = src[k];
+            ga.words[k] = (uint32_t)(k == 7 ? (size_t)v.dm.n_tasks : 2 * n[k]);
+            ga.off[k] = (uint32_t)(2 * off[k]);
+        }
+        return ga;
+    }
+    MargSegments host(const double *h) const {
+        return {h + off[0], h + off[1], h + off[2], h + off[3], h + off[4], h + off[5], h + off[6], reinterpret_cast<const int32_t *>(h + off[7])};
+    }
+};
+
+// a covariance call's two slabs.  results: header | coord_free | frame_cov | lm_var | joint_cov (last: copied back only when the caller wants it);
+// work: S | scale | tiles | sig6 | row_nz, free_coord (int32)
+struct CovSlabs {
+    size_t N, D, max_coords, o_free, o_frame, o_lm, o_joint, n_res, w_scale, w_tiles, w_sig6, w_int, n_work;
+    CovSlabs(size_t N_, size_t M, size_t max_coords_)
+        : N(N_), D(15 * N_), max_coords(max_coords_), o_free(2), o_frame(o_free + (D + 7) / 8), o_lm(o_frame + N * 225), o_joint(o_lm + ((M + 7) & ~(size_t)7)),
+          n_res(o_joint + D * D), w_scale(D * D), w_tiles(w_scale + D), w_sig6(w_tiles + cov_tile_doubles(max_coords)), w_int(w_sig6 + 36 * N * N), n_work(w_int + D) {}
+    CovArgs args(double *d_res, double *d_work) const {
+        CovArgs a{};
+        a.D = (int32_t)D, a.max_coords = (int32_t)max_coords;
+        a.Sfull = d_work, a.scale = d_work + w_scale, a.tiles = d_work + w_tiles, a.sig6 = d_work + w_sig6;
+        a.row_nz = reinterpret_cast<int32_t *>(d_work + w_int), a.free_coord = a.row_nz + D;
+        a.hdr = reinterpret_cast<CovHdr *>(d_res), a.coord_free = reinterpret_cast<uint8_t *>(d_res + o_free);
+        a.frame_cov = d_res + o_frame, a.lm_var = d_res + o_lm, a.joint_cov = d_res + o_joint;
+        return a;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// solve = request buffers -> reset -> [profiling scope] replay the slots until the device reports done (the ranks agreeing
+// on a time limit) -> summary -> unpack.  run_slots replays or captures the graph of enqueue_slot's launch sequence.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// diagnostics (PVIO_HIP_DEBUG_CTRL=1, plain launches only): the control block as each kernel of the slot leaves it
+void BASolver::dump_ctrl(const char *after) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(stream_, &cs);
+    if (!solver_switches().debug_ctrl || cs != hipStreamCaptureStatusNone) return;
+    Ctrl h;
+    (void)hipStreamSynchronize(stream_);
+    (void)hipMemcpy(&h, v_.ctrl, sizeof h, hipMemcpyDeviceToHost);
+    std::fprintf(stderr, "[ctrl after %-11s] mode %d lin_result %d cur %d lin %d iter %d succ %d invalid %d term %d done %d reuse %d solve_ok %d scaling %d trace %d retry %d | radius %.6e mu %.3e x_cost %.9e "
+                         "xn2 %.6e %.6e gmax %.3e | g2 %.6e gn2 %.6e gdot %.6e qvv %.6e qvy %.6e qyy %.6e gy %.6e lm_g2 %.6e | ca %.6e cb %.6e sn %.6e mcc %.6e | it %.6e %.3e %.3e %.3e v%d s%d | fin %d %d %.3e\n",
+                 after, h.mode, h.lin_result, h.cur, h.lin, h.iter, h.num_success, h.invalid_steps, h.termination, h.done, h.reuse, h.solve_ok, h.scaling_ready, h.trace_len, h.retry_relin, h.radius, h.mu, h.x_cost,
+                 h.x_norm2_pose, h.x_norm2_lm, h.grad_max, h.pose_g2, h.pose_gn2, h.pose_gdot, h.pose_qvv, h.pose_qvy, h.pose_qyy, h.pose_gy, h.lm_g2, h.ca, h.cb, h.dogleg_step_norm, h.model_cost_change,
+                 h.it_cost, h.it_cost_change, h.it_step_norm, h.it_rel, h.it_valid, h.it_success, h.fin_flags, h.fin_trace_slot, h.fin_lm_gmax);
+}
+
 int BASolver::enqueue_slot(hipEvent_t *ev) {
     hipError_t e;
     View vl = v_;
@@ -671,27 +766,12 @@ int BASolver::enqueue_slot(hipEvent_t *ev) {
         if ((e = launch_reduce(v_, stream_, 2)) != hipSuccess) return check(e, "k_reduce (image)");
     }
     if (ev) (void)hipEventRecord(ev[3], stream_);
-    // diagnostics (PVIO_HIP_DEBUG_CTRL=1, plain launches only): the control block as each kernel of the slot leaves it
-    static const bool dump_ctrl = std::getenv("PVIO_HIP_DEBUG_CTRL") != nullptr;
-    auto dump = [&](const char *after) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(stream_, &cs);
-        if (!dump_ctrl || cs != hipStreamCaptureStatusNone) return;
-        Ctrl h;
-        (void)hipStreamSynchronize(stream_);
-        (void)hipMemcpy(&h, v_.ctrl, sizeof h, hipMemcpyDeviceToHost);
-        std::fprintf(stderr, "[ctrl after %-11s] mode %d lin_result %d cur %d lin %d iter %d succ %d invalid %d term %d done %d reuse %d solve_ok %d scaling %d trace %d retry %d | radius %.6e mu %.3e x_cost %.9e "
-                             "xn2 %.6e %.6e gmax %.3e | g2 %.6e gn2 %.6e gdot %.6e qvv %.6e qvy %.6e qyy %.6e gy %.6e lm_g2 %.6e | ca %.6e cb %.6e sn %.6e mcc %.6e | it %.6e %.3e %.3e %.3e v%d s%d | fin %d %d %.3e\n",
-                     after, h.mode, h.lin_result, h.cur, h.lin, h.iter, h.num_success, h.invalid_steps, h.termination, h.done, h.reuse, h.solve_ok, h.scaling_ready, h.trace_len, h.retry_relin, h.radius, h.mu, h.x_cost,
-                     h.x_norm2_pose, h.x_norm2_lm, h.grad_max, h.pose_g2, h.pose_gn2, h.pose_gdot, h.pose_qvv, h.pose_qvy, h.pose_qyy, h.pose_gy, h.lm_g2, h.ca, h.cb, h.dogleg_step_norm, h.model_cost_change,
-                     h.it_cost, h.it_cost_change, h.it_step_norm, h.it_rel, h.it_valid, h.it_success, h.fin_flags, h.fin_trace_slot, h.fin_lm_gmax);
-    };
-    dump("k_reduce");
+    dump_ctrl("k_reduce");
     if ((e = launch_dense(v_, stream_)) != hipSuccess) return check(e, "k_dense");
-    dump("k_dense");
+    dump_ctrl("k_dense");
     if (ev) (void)hipEventRecord(ev[4], stream_);
     if (!v_.dm.fuse_backsub && (e = launch_backsub(v_, stream_)) != hipSuccess) return check(e, "k_backsub");
-    dump("k_backsub");
+    dump_ctrl("k_backsub");
     if (ev) (void)hipEventRecord(ev[5], stream_);
     if (sharded_) {
         double *back_local = static_cast<double *>(pool_.get("back_local", kNumBackScal * sizeof(double)));
@@ -711,8 +791,7 @@ int BASolver::run_slots(int n_slots) {
     // 9 257 against 9 779 iterations/s with one rank).  Only ever exercised with a one-rank communicator on this pool, hence the
     // safety net: if capturing or instantiating the sharded graph fails, this context falls back to eager launches for good.
     // PVIO_HIP_SHARDED_GRAPH=0 turns the capture off.
-    static const bool sharded_graph = !(std::getenv("PVIO_HIP_SHARDED_GRAPH") != nullptr && std::atoi(std::getenv("PVIO_HIP_SHARDED_GRAPH")) == 0);
-    if (use_graph_ && (!sharded_ || (sharded_graph && !sharded_graph_failed_)) && (have_graph || solves_since_upload_ > 0)) {
+    if (use_graph_ && (!sharded_ || (solver_switches().sharded_graph && !sharded_graph_failed_)) && (have_graph || solves_since_upload_ > 0)) {
         bool ok = true;
         if (!have_graph) {
             invalidate_graph();
@@ -749,55 +828,191 @@ int BASolver::run_slots(int n_slots) {
     return PVIO_OK;
 }
 
-int BASolver::solve(pvio_ba_summary *sum, pvio_ba_kernel_times *prof, pvio_ba_state *read_back) {
-    if (!uploaded_) return fail(PVIO_ERR_INVALID_ARGUMENT, "no problem uploaded");
-    auto t0 = std::chrono::steady_clock::now();
-    if (check(hipSetDevice(device_), "hipSetDevice")) return PVIO_ERR_HIP;
-    const Dims &dm = v_.dm;
-    const size_t Ns = dm.N, Ms = std::max(dm.M, 1);
-    // fused read-back: frame states, inverse depths, quality, valid bytes in one pinned buffer
-    const size_t n_pack = Ns * 16 + 2 * (size_t)dm.M + ((size_t)dm.M + 7) / 8;
-    double *d_pack = nullptr;
+// the buffers a solve asks for by itself: the packed read-back (device + pinned) and the trace states
+int BASolver::request_solve_buffers(const SolvePack &pack, bool read_back, bool want_states, double **d_pack) {
     if (read_back) {
         bool grew = false;
-        if (!dev(pool_, "result_pack", n_pack, &d_pack, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "result_pack");
-        if (!h_pack_.reserve(n_pack * sizeof(double), (n_pack + n_pack / 2) * sizeof(double))) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+        if (!dev(pool_, "result_pack", pack.n, d_pack, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "result_pack");
+        if (!h_pack_.reserve(pack.n * sizeof(double), (pack.n + pack.n / 2) * sizeof(double))) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
     }
-    double *const h_pack = h_pack_.as<double>();
     // trace states are optional and live in a separate buffer so that bench runs do not pay for them
-    const bool want_states = sum && sum->trace_states && sum->trace_capacity > 0;
-    {
-        double *ts = nullptr;
-        if (want_states) {
-            bool grew = false;
-            if (!dev(pool_, "trace_states", (size_t)trace_cap_ * (Ns * 16 + dm.M), &ts, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "trace_states");
-        }
-        if (ts != v_.trace_states) {
-            v_.trace_states = ts;
-            invalidate_graph();
-        }
-    }
-    // reset: state buffer 0 <- initial state, user state, control block
-    // (one launch: k_reset; the control block's template lives on the device and is sent again only when it changes)
-    {
-        Ctrl t;
-        std::memset(&t, 0, sizeof t);
-        t.mode = MODE_INIT;
-        t.radius = 1e4;        // initial_trust_region_radius
-        t.mu = 1e-8;           // DoglegStrategy kMinMu
-        t.termination = PVIO_TERM_NO_CONVERGENCE;
-        t.trace_cap = trace_cap_;
-        t.dbg_fail_left = dbg_fail_, t.dbg_invalid_left = dbg_invalid_;
+    double *ts = nullptr;
+    if (want_states) {
         bool grew = false;
-        Ctrl *d_tmpl = nullptr;
-        if (!dev(pool_, "ctrl_template", 1, &d_tmpl, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "ctrl template");
-        if (grew || d_tmpl != d_ctrl_tmpl_ || std::memcmp(&t, &h_ctrl_tmpl_, sizeof t) != 0) {
-            h_ctrl_tmpl_ = t, d_ctrl_tmpl_ = d_tmpl;
-            // (pageable source: the copy is staged by the runtime before the call returns)
-            if (check(hipMemcpyAsync(d_tmpl, &h_ctrl_tmpl_, sizeof t, hipMemcpyHostToDevice, stream_), "ctrl template")) return PVIO_ERR_HIP;
-        }
-        if (check(launch_reset(v_, fs_init_, rho_init_, d_tmpl, stream_), "k_reset")) return PVIO_ERR_HIP;
+        if (!dev(pool_, "trace_states", (size_t)trace_cap_ * ((size_t)v_.dm.N * 16 + v_.dm.M), &ts, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "trace_states");
     }
+    if (ts != v_.trace_states) {
+        v_.trace_states = ts;
+        invalidate_graph();
+    }
+    return PVIO_OK;
+}
+
+// reset: state buffer 0 <- initial state, user state, control block
+// (one launch: k_reset; the control block's template lives on the device and is sent again only when it changes)
+int BASolver::reset_for_solve() {
+    Ctrl t;
+    std::memset(&t, 0, sizeof t);
+    t.mode = MODE_INIT;
+    t.radius = 1e4;        // initial_trust_region_radius
+    t.mu = 1e-8;           // DoglegStrategy kMinMu
+    t.termination = PVIO_TERM_NO_CONVERGENCE;
+    t.trace_cap = trace_cap_;
+    t.dbg_fail_left = dbg_fail_, t.dbg_invalid_left = dbg_invalid_;
+    bool grew = false;
+    Ctrl *d_tmpl = nullptr;
+    if (!dev(pool_, "ctrl_template", 1, &d_tmpl, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "ctrl template");
+    if (grew || d_tmpl != d_ctrl_tmpl_ || std::memcmp(&t, &h_ctrl_tmpl_, sizeof t) != 0) {
+        h_ctrl_tmpl_ = t, d_ctrl_tmpl_ = d_tmpl;
+        // (pageable source: the copy is staged by the runtime before the call returns)
+        if (check(hipMemcpyAsync(d_tmpl, &h_ctrl_tmpl_, sizeof t, hipMemcpyHostToDevice, stream_), "ctrl template")) return PVIO_ERR_HIP;
+    }
+    return check(launch_reset(v_, fs_init_, rho_init_, d_tmpl, stream_), "k_reset");
+}
+
+// solve(prof != nullptr): seven events around a slot's launches, the stamp buffer in v_.dbg / v_.dbg_sel and, with PVIO_HIP_PROFILE_GRAPH, a slot graph that
+// carries it.  The destructor undoes all of it on every way out of solve().  Without `prof` the scope does nothing.
+class BASolver::ProfileScope {
+  public:
+    ProfileScope(BASolver &s, pvio_ba_kernel_times *prof) : s_(s), prof_(prof), dbg_saved_(s.v_.dbg), sel_saved_(s.v_.dbg_sel) {}
+    ProfileScope(const ProfileScope &) = delete;
+    ~ProfileScope() {
+        if (!prof_) return;
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        s_.v_.dbg = dbg_saved_, s_.v_.dbg_sel = sel_saved_;
+        if (graph) s_.invalidate_graph(); // the next solve captures a graph without the stamp buffer again
+    }
+    int begin() {
+        if (!prof_) return PVIO_OK;
+        std::memset(prof_, 0, sizeof *prof_);
+        for (auto &e : ev) (void)hipEventCreate(&e);
+        bool grew = false;
+        long long *dbg = nullptr;
+        if (!dev(s_.pool_, "dbg", 4 * 32, &dbg, &grew)) return s_.fail(PVIO_ERR_OUT_OF_MEMORY, "dbg");
+        (void)hipMemsetAsync(dbg, 0, 4 * 32 * sizeof(long long), s_.stream_);
+        // PVIO_HIP_STAMP_SEL: -1 (default) every stamp site stores, k >= 0 only site k (one store per launch), -2 none (events only)
+        const char *sel = std::getenv("PVIO_HIP_STAMP_SEL");
+        s_.v_.dbg_sel = sel ? std::atoi(sel) : -1;
+        s_.v_.dbg = s_.v_.dbg_sel == -2 ? nullptr : dbg;
+        // PVIO_HIP_PROFILE_GRAPH=1: the stamps are taken inside a REPLAY of the slot graph (kernels back to back, as in a normal
+        // solve) instead of eager launches with a host synchronization per slot; no per-launch events then
+        graph = std::getenv("PVIO_HIP_PROFILE_GRAPH") != nullptr && std::atoi(std::getenv("PVIO_HIP_PROFILE_GRAPH")) != 0;
+        if (graph) s_.invalidate_graph(); // the graph bakes the View in: capture one that carries the stamp buffer
+        return PVIO_OK;
+    }
+    bool eager() const { return prof_ && !graph; } // one slot at a time, events around every launch
+    void read_stamps() {
+        if (prof_ && s_.v_.dbg) (void)hipMemcpy(prof_->phase_ticks, s_.v_.dbg, 4 * 32 * sizeof(long long), hipMemcpyDeviceToHost);
+    }
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool graph = false;
+
+  private:
+    BASolver &s_;
+    pvio_ba_kernel_times *prof_;
+    long long *dbg_saved_;
+    int sel_saved_;
+};
+
+// one profiled eager slot: events around every launch; counts only slots that did work
+int BASolver::profiled_slot(hipEvent_t *pev, pvio_ba_kernel_times *prof) {
+    int rc = enqueue_slot(pev);
+    if (rc == PVIO_OK && check(hipStreamSynchronize(stream_), "profile sync")) rc = PVIO_ERR_HIP;
+    if (rc != PVIO_OK) return rc;
+    const int ia[4] = {0, 1, 3, 4}, ib[4] = {1, 2, 4, 5};
+    for (int k = 0; k < 4; ++k) {
+        float ms1 = 0;
+        (void)hipEventElapsedTime(&ms1, pev[ia[k]], pev[ib[k]]);
+        prof->total_ms[k] += ms1;
+        prof->launches[k] += 1;
+    }
+    if (sharded_) { // the two exchange steps: between k_reduce and k_dense, behind k_backsub
+        const int ca[2] = {2, 5}, cb[2] = {3, 6};
+        for (int k = 0; k < 2; ++k) {
+            float ms1 = 0;
+            (void)hipEventElapsedTime(&ms1, pev[ca[k]], pev[cb[k]]);
+            prof->comm_ms[k] += ms1;
+            prof->comm_launches[k] += 1;
+        }
+    }
+    return PVIO_OK;
+}
+
+// max_solver_time_in_seconds (solver_options.h:30): the state machine runs on the device, so the wall clock is looked at
+// between replays of the slot graph only (one replay covers every iteration of an ordinary solve): NO_CONVERGENCE at
+// the iterate reached, like Ceres' time-limit exit.  `timed_out`: what every rank agreed on.
+int BASolver::time_limit_reached(Clock::time_point t0, bool *timed_out) {
+    int out = std::chrono::duration<double>(Clock::now() - t0).count() > max_solver_time_ ? 1 : 0;
+    const int dbg_timeout_rank = solver_switches().timeout_rank;
+    if (dbg_timeout_rank >= 0) out = rank_ == dbg_timeout_rank ? 1 : 0;
+    if (sharded_) {
+        // every rank looks at its OWN clock, but the next replay contains collectives: a rank that left alone would leave the
+        // others waiting in an all-reduce for good.  `done` is identical on all ranks (identical all-reduced inputs),
+        // so they all arrive here in the same round; the decision is all-reduced (max) before anybody acts on it.
+        double *flag = static_cast<double *>(pool_.get("timeout_flag", sizeof(double)));
+        double hflag = out;
+        if (!flag || check(hipMemcpyAsync(flag, &hflag, sizeof(double), hipMemcpyHostToDevice, stream_), "timeout flag H2D")) return PVIO_ERR_HIP;
+        if (comm_allreduce(comm_, flag, 1, 1, stream_)) return fail(PVIO_ERR_COMM, "all-reduce failed");
+        if (check(hipMemcpyAsync(&hflag, flag, sizeof(double), hipMemcpyDeviceToHost, stream_), "timeout flag D2H")) return PVIO_ERR_HIP;
+        if (check(hipStreamSynchronize(stream_), "timeout flag sync")) return PVIO_ERR_HIP;
+        out = hflag > 0.0;
+    }
+    *timed_out = out != 0;
+    return PVIO_OK;
+}
+
+int BASolver::fill_summary(pvio_ba_summary *sum, bool want_states, Clock::time_point t0) {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ev0_, ev1_);
+    sum->termination = h_ctrl_->termination;
+    sum->is_usable = h_ctrl_->termination != PVIO_TERM_FAILURE;
+    sum->num_iterations = h_ctrl_->iter;
+    sum->num_successful_steps = h_ctrl_->num_success;
+    sum->initial_cost = h_ctrl_->initial_cost;
+    sum->final_cost = h_ctrl_->x_cost;
+    sum->device_seconds = ms * 1e-3;
+    sum->trace_len = 0;
+    if (sum->trace && sum->trace_capacity > 0) {
+        const int n = std::min(std::min(h_ctrl_->trace_len, trace_cap_), sum->trace_capacity);
+        std::vector<TraceRec> tr(n);
+        if (n && check(hipMemcpy(tr.data(), v_.trace, n * sizeof(TraceRec), hipMemcpyDeviceToHost), "trace D2H")) return PVIO_ERR_HIP;
+        static_assert(sizeof(TraceRec) == sizeof(pvio_ba_iteration), "trace layout");
+        std::memcpy(sum->trace, tr.data(), n * sizeof(TraceRec));
+        sum->trace_len = n;
+        if (want_states && n)
+            if (check(hipMemcpy(sum->trace_states, v_.trace_states, (size_t)n * ((size_t)v_.dm.N * 16 + v_.dm.M) * sizeof(double), hipMemcpyDeviceToHost), "trace states D2H")) return PVIO_ERR_HIP;
+    }
+    sum->solve_seconds = std::chrono::duration<double>(Clock::now() - t0).count();
+    return PVIO_OK;
+}
+
+// what the quality pass found, for unpack_results and download(): invalidated landmarks keep their old quality (bundle_adjustor.cpp:294)
+static void copy_quality(pvio_ba_state *st, const double *q, const unsigned char *val, size_t M) {
+    for (size_t l = 0; l < M; ++l) {
+        if (st->lm_valid) st->lm_valid[l] = val[l];
+        if (st->lm_quality && val[l]) st->lm_quality[l] = q[l];
+    }
+}
+
+void BASolver::unpack_results(const SolvePack &pack, pvio_ba_state *read_back) const { // same semantics as download()
+    const double *h_pack = h_pack_.as<double>();
+    if (read_back->frame_state) std::memcpy(read_back->frame_state, h_pack, pack.o_rho * sizeof(double));
+    if (pack.M && read_back->lm_inv_depth) std::memcpy(read_back->lm_inv_depth, h_pack + pack.o_rho, pack.M * sizeof(double));
+    copy_quality(read_back, h_pack + pack.o_quality, reinterpret_cast<const unsigned char *>(h_pack + pack.o_valid), pack.M);
+}
+
+int BASolver::solve(pvio_ba_summary *sum, pvio_ba_kernel_times *prof, pvio_ba_state *read_back) {
+    if (!uploaded_) return fail(PVIO_ERR_INVALID_ARGUMENT, "no problem uploaded");
+    const auto t0 = Clock::now();
+    if (check(hipSetDevice(device_), "hipSetDevice")) return PVIO_ERR_HIP;
+    const Dims &dm = v_.dm;
+    const SolvePack pack(dm);
+    const bool want_states = sum && sum->trace_states && sum->trace_capacity > 0;
+    double *d_pack = nullptr;
+    int rc = request_solve_buffers(pack, read_back != nullptr, want_states, &d_pack);
+    if (rc == PVIO_OK) rc = reset_for_solve();
+    if (rc != PVIO_OK) return rc;
     if (check(hipEventRecord(ev0_, stream_), "event")) return PVIO_ERR_HIP;
     // every slot = one pass of [linearize, reduce, dense, backsub]; iteration 0 + max_iter iterations; relaunch while the device
     // has not reported done
@@ -807,140 +1022,40 @@ int BASolver::solve(pvio_ba_summary *sum, pvio_ba_kernel_times *prof, pvio_ba_st
     // slots instead of once per solve: Ceres tests its limit every iteration
     const bool time_limited = max_solver_time_ > 0 && max_solver_time_ < 1.0e5;
     const int n_slots = time_limited ? std::min(dm.max_iter + 1, 2) : dm.max_iter + 1;
-    int rounds = 0;
-    hipEvent_t pev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    long long *dbg_saved = v_.dbg;
-    bool prof_graph = false;
-    if (prof) {
-        std::memset(prof, 0, sizeof *prof);
-        for (auto &e : pev) (void)hipEventCreate(&e);
-        bool grew = false;
-        long long *dbg = nullptr;
-        if (!dev(pool_, "dbg", 4 * 32, &dbg, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "dbg");
-        (void)hipMemsetAsync(dbg, 0, 4 * 32 * sizeof(long long), stream_);
-        // PVIO_HIP_STAMP_SEL: -1 (default) every stamp site stores, k >= 0 only site k (one store per launch), -2 none (events only)
-        const char *sel = std::getenv("PVIO_HIP_STAMP_SEL");
-        v_.dbg_sel = sel ? std::atoi(sel) : -1;
-        v_.dbg = v_.dbg_sel == -2 ? nullptr : dbg;
-        // PVIO_HIP_PROFILE_GRAPH=1: the stamps are taken inside a REPLAY of the slot graph (kernels back to back, as in a normal
-        // solve) instead of eager launches with a host synchronization per slot; no per-launch events then
-        prof_graph = std::getenv("PVIO_HIP_PROFILE_GRAPH") != nullptr && std::atoi(std::getenv("PVIO_HIP_PROFILE_GRAPH")) != 0;
-        if (prof_graph) invalidate_graph(); // the graph bakes the View in: capture one that carries the stamp buffer
-    }
-    for (;;) {
-        int rc;
-        if (prof && !prof_graph) { // one slot at a time, events around every launch; counts only slots that did work
-            rc = enqueue_slot(pev);
-            if (rc == PVIO_OK && check(hipStreamSynchronize(stream_), "profile sync")) rc = PVIO_ERR_HIP;
-            if (rc == PVIO_OK) {
-                const int ia[4] = {0, 1, 3, 4}, ib[4] = {1, 2, 4, 5};
-                for (int k = 0; k < 4; ++k) {
-                    float ms1 = 0;
-                    (void)hipEventElapsedTime(&ms1, pev[ia[k]], pev[ib[k]]);
-                    prof->total_ms[k] += ms1;
-                    prof->launches[k] += 1;
-                }
-                if (sharded_) { // the two exchange steps: between k_reduce and k_dense, behind k_backsub
-                    const int ca[2] = {2, 5}, cb[2] = {3, 6};
-                    for (int k = 0; k < 2; ++k) {
-                        float ms1 = 0;
-                        (void)hipEventElapsedTime(&ms1, pev[ca[k]], pev[cb[k]]);
-                        prof->comm_ms[k] += ms1;
-                        prof->comm_launches[k] += 1;
-                    }
-                }
+    {
+        ProfileScope profile(*this, prof);
+        if ((rc = profile.begin()) != PVIO_OK) return rc;
+        for (int rounds = 0;;) {
+            rc = profile.eager() ? profiled_slot(profile.ev, prof) : run_slots(n_slots);
+            if (profile.eager()) --rounds; // the round cap below is for graph replays
+            if (rc != PVIO_OK) return rc;
+            const auto t_enq = Clock::now();
+            if (check(hipMemcpyAsync(h_ctrl_, v_.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, stream_), "ctrl D2H")) return PVIO_ERR_HIP;
+            if (check(hipEventRecord(ev1_, stream_), "event")) return PVIO_ERR_HIP;
+            if (read_back) { // speculative: all but never is the state machine still running after one replay (then this is repeated)
+                if (check(launch_quality(v_, stream_, 1, nullptr, d_pack), "k_quality")) return PVIO_ERR_HIP;
+                if (check(hipMemcpyAsync(h_pack_.data(), d_pack, pack.n * sizeof(double), hipMemcpyDeviceToHost, stream_), "results D2H")) return PVIO_ERR_HIP;
             }
-            --rounds; // the round cap below is for graph replays
-        } else {
-            rc = run_slots(n_slots);
-        }
-        if (rc != PVIO_OK) return rc;
-        const auto t_enq = std::chrono::steady_clock::now();
-        if (check(hipMemcpyAsync(h_ctrl_, v_.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, stream_), "ctrl D2H")) return PVIO_ERR_HIP;
-        if (check(hipEventRecord(ev1_, stream_), "event")) return PVIO_ERR_HIP;
-        if (read_back) { // speculative: all but never is the state machine still running after one replay (then this is repeated)
-            if (check(launch_quality(v_, stream_, 1, nullptr, d_pack), "k_quality")) return PVIO_ERR_HIP;
-            if (check(hipMemcpyAsync(h_pack, d_pack, n_pack * sizeof(double), hipMemcpyDeviceToHost, stream_), "results D2H")) return PVIO_ERR_HIP;
-        }
-        if (check(hipStreamSynchronize(stream_), "solve sync")) return PVIO_ERR_HIP;
-        stage_in_flight_ = false;
-        {   // PVIO_HIP_TIMING=1: where the host's time of a solve goes (enqueueing the slots against waiting for them)
-            static const bool timing = std::getenv("PVIO_HIP_TIMING") != nullptr;
-            if (timing)
-                std::fprintf(stderr, "[pvio-hip] solve host: reset + %d slots enqueued after %.0f us (%s), stream drained after %.0f us\n", n_slots,
-                             std::chrono::duration<double, std::micro>(t_enq - t0).count(), graph_exec_ && graph_slots_ == n_slots ? "graph" : "plain launches",
-                             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
-        }
-        if (h_ctrl_->done || ++rounds > (time_limited ? 16 * (dm.max_iter + 1) : 16)) break;
-        // max_solver_time_in_seconds (solver_options.h:30): the state machine runs on the device, so the wall clock is looked at
-        // between replays of the slot graph only (one replay covers every iteration of an ordinary solve): NO_CONVERGENCE at
-        // the iterate reached, like Ceres' time-limit exit
-        if (max_solver_time_ > 0) {
-            int timed_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > max_solver_time_ ? 1 : 0;
-            // tests: only rank PVIO_HIP_DEBUG_TIMEOUT_RANK sees its clock run out (the ranks must still leave in the same round)
-            static const int dbg_timeout_rank = std::getenv("PVIO_HIP_DEBUG_TIMEOUT_RANK") ? std::atoi(std::getenv("PVIO_HIP_DEBUG_TIMEOUT_RANK")) : -1;
-            if (dbg_timeout_rank >= 0) timed_out = rank_ == dbg_timeout_rank ? 1 : 0;
-            if (sharded_) {
-                // every rank looks at its OWN clock, but the next replay contains collectives: a rank that left alone would leave the
-                // others waiting in an all-reduce for good.  `done` is identical on all ranks (identical all-reduced inputs),
-                // so they all arrive here in the same round; the decision is all-reduced (max) before anybody acts on it.
-                double *flag = static_cast<double *>(pool_.get("timeout_flag", sizeof(double)));
-                double hflag = timed_out;
-                if (!flag || check(hipMemcpyAsync(flag, &hflag, sizeof(double), hipMemcpyHostToDevice, stream_), "timeout flag H2D")) return PVIO_ERR_HIP;
-                if (comm_allreduce(comm_, flag, 1, 1, stream_)) return fail(PVIO_ERR_COMM, "all-reduce failed");
-                if (check(hipMemcpyAsync(&hflag, flag, sizeof(double), hipMemcpyDeviceToHost, stream_), "timeout flag D2H")) return PVIO_ERR_HIP;
-                if (check(hipStreamSynchronize(stream_), "timeout flag sync")) return PVIO_ERR_HIP;
-                timed_out = hflag > 0.0;
-            }
+            if (check(hipStreamSynchronize(stream_), "solve sync")) return PVIO_ERR_HIP;
+            stage_in_flight_ = false;
+            if (solver_switches().timing) // PVIO_HIP_TIMING=1: where the host's time of a solve goes (enqueueing the slots against waiting for them)
+                std::fprintf(stderr, "[pvio-hip] solve host: reset + %d slots enqueued after %.0f us (%s), stream drained after %.0f us\n", n_slots, us(t0, t_enq),
+                             graph_exec_ && graph_slots_ == n_slots ? "graph" : "plain launches", us(t0, Clock::now()));
+            if (h_ctrl_->done || ++rounds > (time_limited ? 16 * (dm.max_iter + 1) : 16)) break;
+            bool timed_out = false;
+            if (max_solver_time_ > 0 && (rc = time_limit_reached(t0, &timed_out)) != PVIO_OK) return rc;
             if (timed_out) {
                 h_ctrl_->done = 1, h_ctrl_->termination = PVIO_TERM_NO_CONVERGENCE;
                 break;
             }
         }
-    }
-    if (prof) {
-        for (auto &e : pev) (void)hipEventDestroy(e);
-        if (v_.dbg) (void)hipMemcpy(prof->phase_ticks, v_.dbg, 4 * 32 * sizeof(long long), hipMemcpyDeviceToHost);
-        v_.dbg = dbg_saved;
-        if (prof_graph) invalidate_graph(); // the next solve captures a graph without the stamp buffer again
+        profile.read_stamps();
     }
     ++solves_since_upload_;
     if (!h_ctrl_->done) return fail(PVIO_ERR_HIP, "device state machine did not terminate");
     last_repeats_ = h_ctrl_->cand_repeats;
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ev0_, ev1_);
-    if (sum) {
-        sum->termination = h_ctrl_->termination;
-        sum->is_usable = h_ctrl_->termination != PVIO_TERM_FAILURE;
-        sum->num_iterations = h_ctrl_->iter;
-        sum->num_successful_steps = h_ctrl_->num_success;
-        sum->initial_cost = h_ctrl_->initial_cost;
-        sum->final_cost = h_ctrl_->x_cost;
-        sum->device_seconds = ms * 1e-3;
-        sum->trace_len = 0;
-        if (sum->trace && sum->trace_capacity > 0) {
-            const int n = std::min(std::min(h_ctrl_->trace_len, trace_cap_), sum->trace_capacity);
-            std::vector<TraceRec> tr(n);
-            if (n && check(hipMemcpy(tr.data(), v_.trace, n * sizeof(TraceRec), hipMemcpyDeviceToHost), "trace D2H")) return PVIO_ERR_HIP;
-            static_assert(sizeof(TraceRec) == sizeof(pvio_ba_iteration), "trace layout");
-            std::memcpy(sum->trace, tr.data(), n * sizeof(TraceRec));
-            sum->trace_len = n;
-            if (want_states && n)
-                if (check(hipMemcpy(sum->trace_states, v_.trace_states, (size_t)n * (Ns * 16 + dm.M) * sizeof(double), hipMemcpyDeviceToHost), "trace states D2H")) return PVIO_ERR_HIP;
-        }
-        sum->solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    if (read_back) { // same semantics as download(): invalidated landmarks keep their old quality (bundle_adjustor.cpp:294)
-        const size_t M = dm.M;
-        if (read_back->frame_state) std::memcpy(read_back->frame_state, h_pack, Ns * 16 * sizeof(double));
-        if (M && read_back->lm_inv_depth) std::memcpy(read_back->lm_inv_depth, h_pack + Ns * 16, M * sizeof(double));
-        const double *q = h_pack + Ns * 16 + M;
-        const unsigned char *val = reinterpret_cast<const unsigned char *>(h_pack + Ns * 16 + 2 * M);
-        for (size_t l = 0; l < M; ++l) {
-            if (read_back->lm_valid) read_back->lm_valid[l] = val[l];
-            if (read_back->lm_quality && val[l]) read_back->lm_quality[l] = q[l];
-        }
-    }
+    if (sum && (rc = fill_summary(sum, want_states, t0)) != PVIO_OK) return rc;
+    if (read_back) unpack_results(pack, read_back);
     return PVIO_OK;
 }
 
@@ -959,10 +1074,7 @@ int BASolver::download(pvio_ba_state *st) {
             if (check(hipMemcpyAsync(q.data(), v_.lm_quality, (size_t)dm.M * sizeof(double), hipMemcpyDeviceToHost, stream_), "D2H")) return PVIO_ERR_HIP;
             if (check(hipMemcpyAsync(val.data(), v_.lm_valid, (size_t)dm.M, hipMemcpyDeviceToHost, stream_), "D2H")) return PVIO_ERR_HIP;
             if (check(hipStreamSynchronize(stream_), "sync")) return PVIO_ERR_HIP;
-            for (int l = 0; l < dm.M; ++l) {
-                if (st->lm_valid) st->lm_valid[l] = val[l];
-                if (st->lm_quality && val[l]) st->lm_quality[l] = q[l]; // invalidated landmarks keep their old quality (:294)
-            }
+            copy_quality(st, q.data(), val.data(), (size_t)dm.M);
         }
     }
     return check(hipStreamSynchronize(stream_), "download sync");
@@ -986,44 +1098,24 @@ int BASolver::reprojection_error(double *out) {
     return PVIO_OK;
 }
 
-} // namespace pvba
+// ---------------------------------------------------------------------------------------------------------------------
+// The one-shot calls: marginalize and covariance = upload -> linearize_once -> their own kernels and read-back.  Both use
+// the uploaded window up: from their upload on the context is between windows, whichever way they return.
+// ---------------------------------------------------------------------------------------------------------------------
 
-namespace pvba {
-
-static bool lu_inverse15(const double *Ain, double *inv) { // Eigen's .inverse() for a 15 x 15 block is PartialPivLU based
-    const int n = 15;
-    double A[225];
-    int piv[15];
-    std::memcpy(A, Ain, sizeof A);
-    for (int i = 0; i < n; ++i) piv[i] = i;
-    for (int k = 0; k < n; ++k) {
-        int p = k;
-        double best = std::fabs(A[k * n + k]);
-        for (int i = k + 1; i < n; ++i)
-            if (std::fabs(A[i * n + k]) > best) best = std::fabs(A[i * n + k]), p = i;
-        if (best == 0.0) return false;
-        if (p != k) {
-            for (int j = 0; j < n; ++j) std::swap(A[k * n + j], A[p * n + j]);
-            std::swap(piv[k], piv[p]);
-        }
-        for (int i = k + 1; i < n; ++i) {
-            const double f = A[i * n + k] / A[k * n + k];
-            A[i * n + k] = f;
-            for (int j = k + 1; j < n; ++j) A[i * n + j] -= f * A[k * n + j];
-        }
-    }
-    for (int col = 0; col < n; ++col) {
-        double x[15];
-        for (int i = 0; i < n; ++i) x[i] = piv[i] == col ? 1.0 : 0.0;
-        for (int i = 0; i < n; ++i)
-            for (int k = 0; k < i; ++k) x[i] -= A[i * n + k] * x[k];
-        for (int i = n - 1; i >= 0; --i) {
-            for (int k = i + 1; k < n; ++k) x[i] -= A[i * n + k] * x[k];
-            x[i] /= A[i * n + i];
-        }
-        for (int i = 0; i < n; ++i) inv[i * n + col] = x[i];
-    }
-    return true;
+// One undamped linearization of the window just uploaded, at the uploaded state: k_reset, the control block, k_linearize, k_reduce.
+int BASolver::linearize_once(int mode, int victim) {
+    // working states <- the uploaded ones, in one launch (the control block it also copies is its own content: overwritten right below)
+    if (check(launch_reset(v_, fs_init_, rho_init_, v_.ctrl, stream_), "k_reset")) return PVIO_ERR_HIP;
+    std::memset(h_ctrl_, 0, sizeof(Ctrl));
+    h_ctrl_->mode = mode;
+    h_ctrl_->marg_victim = victim;
+    h_ctrl_->mu = 0.0; // no damping: the Schur weight of a landmark is 1 / H_ll
+    if (check(hipMemcpyAsync(v_.ctrl, h_ctrl_, sizeof(Ctrl), hipMemcpyHostToDevice, stream_), "ctrl")) return PVIO_ERR_HIP;
+    hipError_t e;
+    if ((e = launch_linearize(v_, stream_)) != hipSuccess) return check(e, "k_linearize");
+    if ((e = launch_reduce(v_, stream_, sharded_ ? 1 : 0)) != hipSuccess) return check(e, "k_reduce");
+    return PVIO_OK;
 }
 
 // The landmarks of the window that the victim observes (anchor or target), in their order, with their CSR rows, multiplicities and inverse depths.
@@ -1055,18 +1147,33 @@ static bool marg_subset(const pvio_ba_problem *pb, const pvio_ba_state *st, int 
     return true;
 }
 
+// read-back as ONE copy into a pinned buffer: a D2H copy into pageable memory is staged synchronously by the runtime (about 20 us
+// each, eight of them); the eight arrays are gathered on the device first (k_gather).  Synchronizes.
+int BASolver::read_back_marg(const MargGather &lay, const double **h_out) {
+    double *const h_back = static_cast<double *>(h_back_.reserve(lay.total() * sizeof(double), (lay.total() + lay.total() / 2) * sizeof(double)));
+    if (!h_back) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+    double *d_back = nullptr;
+    bool grew = false;
+    if (!dev(pool_, "marg_back", lay.total(), &d_back, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "marg_back");
+    if (check(launch_gather(lay.args(v_), d_back, stream_), "k_gather")) return PVIO_ERR_HIP;
+    if (check(hipMemcpyAsync(h_back, d_back, lay.total() * sizeof(double), hipMemcpyDeviceToHost, stream_), "D2H")) return PVIO_ERR_HIP;
+    if (check(hipStreamSynchronize(stream_), "marginalize sync")) return PVIO_ERR_HIP;
+    stage_in_flight_ = false;
+    *h_out = h_back;
+    return PVIO_OK;
+}
+
 // BundleAdjustor::marginalize_frame (bundle_adjustor.cpp:348-599).  The O(F) part -- un-robustified J^T J / J^T r of
 // every reprojection factor of the victim's landmarks, the scalar landmark elimination, the prior and the two IMU
 // factors -- runs on the GPU through k_linearize (MODE_MARG) + k_reduce; the 15N-dimensional dense tail (victim block
-// elimination, eigen-decomposition) is a few hundred kflop and stays on the host.
+// elimination, eigen-decomposition: marg_prior.h) is a few hundred kflop and stays on the host.
 int BASolver::marginalize(const pvio_ba_problem *pb, const pvio_ba_state *st, int victim, pvio_ba_prior *out) {
     if (!pb || !st || !out || !out->S || !out->s) return fail(PVIO_ERR_INVALID_ARGUMENT, "null argument");
-    const int N = pb->n_frames;
+    const int N = pb->n_frames, R = 15 * (N - 1);
     if (victim < 0 || victim >= N || N < 2) return fail(PVIO_ERR_INVALID_ARGUMENT, "victim frame out of range");
+    const auto tm0 = Clock::now();
     // marginalization always works on the full 15-dim error state and ignores FF_FIX_POSE; IMU factors are used
     // whenever they exist (:416-450), regardless of how the last solve was configured
-    static const bool timing = std::getenv("PVIO_HIP_TIMING") != nullptr; // diagnostics: where a marginalization's time goes
-    const auto tm0 = std::chrono::steady_clock::now();
     pvio_ba_problem p2 = *pb;
     p2.use_inertial = 1;
     // :453-461: the problem is built from the tracks the victim observes (as their anchor or as a target) and from nothing else -- the other tracks
@@ -1082,229 +1189,65 @@ int BASolver::marginalize(const pvio_ba_problem *pb, const pvio_ba_state *st, in
         p2.lm_multiplicity = pb->lm_multiplicity ? k_mult.data() : nullptr;
         st2.lm_inv_depth = k_rho.data();
     }
-    int rc = upload(&p2, &st2, /*may_return_early=*/true); // (this call synchronizes below, before the caller's arrays can change)
+    int rc = upload(&p2, &st2, /*may_return_early=*/true); // (read_back_marg synchronizes, before the caller's arrays can change)
     if (rc != PVIO_OK) return rc;
-    const auto tm1 = std::chrono::steady_clock::now();
+    uploaded_ = false; // the device buffers are about to hold a marginalization pass, not a solvable window: whichever way this call ends
+    const auto tm1 = Clock::now();
+    if ((rc = linearize_once(MODE_MARG, victim)) != PVIO_OK) return rc;
     const Dims &dm = v_.dm;
-    const size_t Ns = N;
-    const double *fs_init = fs_init_, *rho_init = rho_init_;
-    // working states <- the uploaded ones, in one launch (the control block it also copies is its own content: overwritten right below)
-    if (check(launch_reset(v_, fs_init, rho_init, v_.ctrl, stream_), "k_reset")) return PVIO_ERR_HIP;
-    std::memset(h_ctrl_, 0, sizeof(Ctrl));
-    h_ctrl_->mode = MODE_MARG;
-    h_ctrl_->marg_victim = victim;
-    h_ctrl_->mu = 0.0;
-    if (check(hipMemcpyAsync(v_.ctrl, h_ctrl_, sizeof(Ctrl), hipMemcpyHostToDevice, stream_), "ctrl")) return PVIO_ERR_HIP;
-    hipError_t e;
-    if ((e = launch_linearize(v_, stream_)) != hipSuccess) return check(e, "k_linearize");
-    if ((e = launch_reduce(v_, stream_, sharded_ ? 1 : 0)) != hipSuccess) return check(e, "k_reduce");
-    const size_t nS = (size_t)dm.n_tasks * 9, nV = (size_t)kNumPoseVec * dm.P6;
+    const MargGather lay(dm);
     // landmark shards: every rank holds the victim's landmarks of its own range only -> sum the reduced buffers (the IMU
     // factors, the old prior and the rotation prior are replicated and are added once, below, on every rank alike)
-    if (sharded_ && comm_allreduce(comm_, v_.red, nS + nV + kNumLinScal + (size_t)world_, 0, stream_)) return fail(PVIO_ERR_COMM, "all-reduce failed");
-    // read-back as ONE copy into a pinned buffer: a D2H copy into pageable memory is staged synchronously by the runtime (about 20 us
-    // each, eight of them); the eight arrays are gathered on the device first (k_gather)
-    const size_t Dp = 15 * (size_t)dm.prior_n;
-    const size_t n_back[8] = {nS + nV + kNumLinScal, Ns * 900, Ns * 30, Dp * Dp, Dp, Ns * 9, Ns * 3, ((size_t)dm.n_tasks + 1) / 2};
-    size_t off_back[9] = {0};
-    for (int k = 0; k < 8; ++k) off_back[k + 1] = off_back[k] + ((n_back[k] + 7) & ~(size_t)7);
-    double *const h_back = static_cast<double *>(h_back_.reserve(off_back[8] * sizeof(double), (off_back[8] + off_back[8] / 2) * sizeof(double)));
-    if (!h_back) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
-    const double *red = h_back + off_back[0], *preH = h_back + off_back[1], *preg = h_back + off_back[2], *priH = h_back + off_back[3];
-    const double *prig = h_back + off_back[4], *rotH = h_back + off_back[5], *rotg = h_back + off_back[6];
-    const int32_t *tasks = reinterpret_cast<const int32_t *>(h_back + off_back[7]);
-    const void *src_back[8] = {v_.red, v_.pre_H, v_.pre_g, v_.prior_H, v_.prior_g, v_.rot_H, v_.rot_g, v_.task_desc};
-    GatherArgs ga;
-    for (int k = 0; k < 8; ++k) {
-        ga.src[k] = src_back[k];
-        ga.words[k] = (uint32_t)(k == 7 ? (size_t)dm.n_tasks : 2 * n_back[k]);
-        ga.off[k] = (uint32_t)(2 * off_back[k]);
-    }
-    double *d_back = nullptr;
-    {
-        bool grew = false;
-        if (!dev(pool_, "marg_back", off_back[8], &d_back, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "marg_back");
-    }
-    if (check(launch_gather(ga, d_back, stream_), "k_gather")) return PVIO_ERR_HIP;
-    if (check(hipMemcpyAsync(h_back, d_back, off_back[8] * sizeof(double), hipMemcpyDeviceToHost, stream_), "D2H")) return PVIO_ERR_HIP;
-    if (check(hipStreamSynchronize(stream_), "marginalize sync")) return PVIO_ERR_HIP;
-    stage_in_flight_ = false;
-    const auto tm2 = std::chrono::steady_clock::now();
-
-    // ---- assemble the 15N information matrix / vector ----
-    const int D = 15 * N;
+    if (sharded_ && comm_allreduce(comm_, v_.red, lay.n[0] + (size_t)world_, 0, stream_)) return fail(PVIO_ERR_COMM, "all-reduce failed");
+    const double *h_back = nullptr;
+    if ((rc = read_back_marg(lay, &h_back)) != PVIO_OK) return rc;
+    const auto tm2 = Clock::now();
     // (the large work arrays are members: a fresh 180 KB vector per call is an mmap, its page faults and an munmap)
-    std::vector<double> &H = marg_H_, &C = marg_C_, &V = marg_V_;
-    std::vector<double> b(D, 0.0);
-    H.assign((size_t)D * D, 0.0);
-    for (int t = 0; t < dm.n_tasks; ++t) {
-        const int fi = tasks[t] & 255, fj = (tasks[t] >> 8) & 255, si = (tasks[t] >> 16) & 1, sj = (tasks[t] >> 17) & 1;
-        for (int el = 0; el < 9; ++el) {
-            const int r = 15 * fi + 3 * si + el / 3, c = 15 * fj + 3 * sj + el % 3;
-            const double val = red[(size_t)el * dm.n_tasks + t];
-            if (fi != fj) H[(size_t)r * D + c] = H[(size_t)c * D + r] = val;
-            else if (r >= c) H[(size_t)r * D + c] = H[(size_t)c * D + r] = val; // only the lower half of a diagonal block is complete
-        }
-    }
-    for (int f = 0; f < N; ++f)
-        for (int k = 0; k < 6; ++k) b[15 * f + k] = red[nS + 6 * f + k] - red[nS + dm.P6 + 6 * f + k]; // J^T r - sum_l W_l^T b_l / H_ll
-    for (int j = victim; j <= victim + 1; ++j) {
-        if (j == 0 || j >= N || !(pb->preint_valid && pb->preint_valid[j])) continue;
-        for (int a = 0; a < 30; ++a) {
-            b[15 * (j - 1) + a] += preg[(size_t)j * 30 + a];
-            for (int c = 0; c < 30; ++c) H[(size_t)(15 * (j - 1) + a) * D + 15 * (j - 1) + c] += preH[(size_t)j * 900 + a * 30 + c];
-        }
-    }
-    for (int a = 0; a < 3; ++a) { // the victim's rotation prior (evaluated un-gated in MODE_MARG; zero when it has none)
-        b[15 * victim + a] += rotg[(size_t)victim * 3 + a];
-        for (int c = 0; c < 3; ++c) H[(size_t)(15 * victim + a) * D + 15 * victim + c] += rotH[(size_t)victim * 9 + 3 * a + c];
-    }
-    std::vector<int> gprior(Dp); // prior coordinate -> window coordinate (a division per ELEMENT of the 135 x 135 block cost 40 us here)
-    for (size_t a = 0; a < Dp; ++a) gprior[a] = 15 * pb->prior_frames[a / 15] + (int)(a % 15);
-    for (size_t a = 0; a < Dp; ++a) {
-        const int ga = gprior[a];
-        b[ga] += prig[a];
-        double *hrow = &H[(size_t)ga * D];
-        const double *prow = &priH[a * Dp];
-        for (size_t c = 0; c < Dp; ++c) hrow[gprior[c]] += prow[c];
-    }
-    // ---- eliminate the victim's 15 x 15 block (:547-581) ----
-    const int R = D - 15;
-    double Hvv[225], Hinv[225];
-    for (int x = 0; x < 15; ++x)
-        for (int y = 0; y < 15; ++y) Hvv[x * 15 + y] = H[(size_t)(15 * victim + x) * D + 15 * victim + y];
-    if (!lu_inverse15(Hvv, Hinv)) return fail(PVIO_ERR_INVALID_ARGUMENT, "singular victim block");
-    auto gidx = [&](int k) { return k < 15 * victim ? k : k + 15; };
-    std::vector<double> cv(R, 0.0), T((size_t)R * 15);
-    C.assign((size_t)R * R, 0.0);
-    for (int i = 0; i < R; ++i) { // T = H_rv Hvv^-1: fifteen independent sums per row, each still taken over x in ascending order
-        const double *hiv = &H[(size_t)gidx(i) * D + 15 * victim];
-        double trow[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int x = 0; x < 15; ++x) {
-            const double hx = hiv[x];
-            for (int y = 0; y < 15; ++y) trow[y] += hx * Hinv[x * 15 + y];
-        }
-        for (int y = 0; y < 15; ++y) T[(size_t)i * 15 + y] = trow[y];
-    }
-    const int split = 15 * victim;
-    // the victim's rows with the victim's own columns removed, so that the inner loops below run over contiguous memory (the sums are
-    // taken in the same order as a loop over y per element would take them; that form cost 100 us per marginalization)
-    std::vector<double> Hv((size_t)15 * R), acc(R);
-    for (int y = 0; y < 15; ++y)
-        for (int j = 0; j < R; ++j) Hv[(size_t)y * R + j] = H[(size_t)(15 * victim + y) * D + gidx(j)];
-    for (int i = 0; i < R; ++i) {
-        double s = 0;
-        for (int y = 0; y < 15; ++y) s += T[(size_t)i * 15 + y] * b[15 * victim + y];
-        cv[i] = b[gidx(i)] - s;
-        const int j0 = i >= split ? split : 0; // lower-left = transpose of upper-right (:572-576), filled in below
-        for (int j = j0; j < R; ++j) acc[j] = 0;
-        for (int y = 0; y < 15; ++y) {
-            const double ty = T[(size_t)i * 15 + y];
-            const double *hv = &Hv[(size_t)y * R];
-            for (int j = j0; j < R; ++j) acc[j] += ty * hv[j];
-        }
-        const double *hi = &H[(size_t)gidx(i) * D];
-        double *ci = &C[(size_t)i * R];
-        for (int j = j0; j < split; ++j) ci[j] = hi[j] - acc[j];
-        for (int j = j0 > split ? j0 : split; j < R; ++j) ci[j] = hi[j + 15] - acc[j];
-    }
-    for (int i = split; i < R; ++i)
-        for (int j = 0; j < split; ++j) C[(size_t)i * R + j] = C[(size_t)j * R + i];
-    if (out->info_matrix) std::memcpy(out->info_matrix, C.data(), sizeof(double) * R * R);
+    std::vector<double> b, cv;
+    assemble_information(lay.host(h_back), pb->preint_valid, pb->prior_frames, dm.prior_n, N, victim, dm.n_tasks, dm.P6, marg_H_, b);
+    if (!eliminate_victim(marg_H_, b, N, victim, marg_C_, cv)) return fail(PVIO_ERR_INVALID_ARGUMENT, "singular victim block");
+    if (out->info_matrix) std::memcpy(out->info_matrix, marg_C_.data(), sizeof(double) * R * R); // (before sqrt_information uses C up)
     if (out->info_vector) std::memcpy(out->info_vector, cv.data(), sizeof(double) * R);
-    // ---- sqrt information: sqrt(L) V^T and L^-1/2 V^T b, eigenvalues <= 1e-8 zeroed (:583-590) ----
-    // Coordinates without any information -- an exactly zero row and column: velocity / biases of a frame no IMU factor or prior reaches --
-    // are eigenvectors of eigenvalue 0 by themselves and stay out of the eigen-problem: a backward-stable solver would hand them back with
-    // an eigenvalue of a few eps |C| and a few eps of every other coordinate mixed in, which the 1e-8 cut then keeps or drops as the rounding
-    // falls (profiles/NOTES_r1_r3.md section 2a).  Their rows of S are zero (they come first, like the zero eigenvalues of the full problem).
-    std::vector<int> keep;
-    keep.reserve(R);
-    for (int i = 0; i < R; ++i) {
-        bool zero = true;
-        for (int j = 0; j < R && zero; ++j) zero = C[(size_t)i * R + j] == 0.0 && C[(size_t)j * R + i] == 0.0;
-        if (!zero) keep.push_back(i);
-    }
-    const int Rk = (int)keep.size(), nz = R - Rk;
-    std::vector<double> w(std::max(Rk, 1));
-    V.resize((size_t)std::max(Rk, 1) * std::max(Rk, 1));
-    const auto tm3 = std::chrono::steady_clock::now();
-    if (nz > 0) { // compress the kept coordinates to the front of C's storage (the copies above have been made)
-        for (int a = 0; a < Rk; ++a)
-            for (int b = 0; b < Rk; ++b) C[(size_t)a * Rk + b] = C[(size_t)keep[a] * R + keep[b]];
-    }
-    if (Rk > 0) sym_eig(C.data(), Rk, w.data(), V.data());
-    const auto tm4 = std::chrono::steady_clock::now();
     out->n = N - 1;
-    std::fill(out->S, out->S + (size_t)R * R, 0.0);
-    std::fill(out->s, out->s + R, 0.0);
-    for (int k = 0; k < Rk; ++k) {
-        const double lam = w[k] > 1.0e-8 ? w[k] : 0.0, lam_inv = w[k] > 1.0e-8 ? 1.0 / w[k] : 0.0;
-        const double sl = std::sqrt(lam), sli = std::sqrt(lam_inv);
-        double acc = 0;
-        double *Srow = out->S + (size_t)(nz + k) * R;
-        for (int i = 0; i < Rk; ++i) {
-            Srow[keep[i]] = sl * V[(size_t)k * Rk + i];
-            acc += V[(size_t)k * Rk + i] * cv[keep[i]];
-        }
-        out->s[nz + k] = sli * acc;
-    }
-    uploaded_ = false; // the device buffers now hold a marginalization pass, not a solvable window
-    if (timing) {
-        auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    const SqrtInfoStats eig = sqrt_information(marg_C_, cv, R, marg_V_, out->S, out->s);
+    if (solver_switches().timing) // diagnostics: where a marginalization's time goes
         std::fprintf(stderr, "[pvio-hip] marginalize: upload %.0f us, kernels + read-back %.0f us, assembly + elimination %.0f us, eigen-decomposition (%d x %d) %.0f us, sqrt-information %.0f us\n",
-                     us(tm0, tm1), us(tm1, tm2), us(tm2, tm3), Rk, Rk, us(tm3, tm4), us(tm4, std::chrono::steady_clock::now()));
-    }
+                     us(tm0, tm1), us(tm1, tm2), us(tm2, eig.eig_begin), eig.Rk, eig.Rk, us(eig.eig_begin, eig.eig_end), us(eig.eig_end, Clock::now()));
     return PVIO_OK;
 }
 
-// Marginal covariances of the window at `st` (pvio_hip_ba_covariance; no reference counterpart).  The first half is marginalize()'s -- upload, reset,
-// one undamped linearization, the reduction -- in MODE_INIT over the whole window: the robustified, multiplicity-weighted J^T J the solver's own
+// Marginal covariances of the window at `st` (pvio_hip_ba_covariance; no reference counterpart).  The first half is marginalize()'s -- upload and
+// linearize_once -- in MODE_INIT over the whole window: the robustified, multiplicity-weighted J^T J the solver's own
 // iteration 0 sees, constant blocks constant.  The kernels of ba_cov.hip then assemble, scale, invert and scatter on the solver's stream; the
 // results come back as ONE copy through a pinned buffer.
 int BASolver::covariance(const pvio_ba_problem *pb, const pvio_ba_state *st, pvio_ba_covariance *out) {
     if (!pb || !st || !out || !out->frame_cov) return fail(PVIO_ERR_INVALID_ARGUMENT, "null argument");
     if (sharded_) return fail(PVIO_ERR_UNSUPPORTED, "pvio_hip_ba_covariance: landmark-sharded contexts are not supported");
-    static const bool timing = std::getenv("PVIO_HIP_TIMING") != nullptr; // diagnostics: hipEvents around the three kernels
+    const bool timing = solver_switches().timing; // diagnostics: hipEvents around the three kernels
     int rc = upload(pb, st, /*may_return_early=*/true); // (this call synchronizes below, before the caller's arrays can change)
     if (rc != PVIO_OK) return rc;
+    uploaded_ = false; // the device buffers are about to hold an undamped linearization, not a solvable window: whichever way this call ends
+    if ((rc = linearize_once(MODE_INIT, 0)) != PVIO_OK) return rc;
     const Dims &dm = v_.dm;
     const size_t N = (size_t)dm.N, M = (size_t)dm.M, D = 15 * N;
-    if (check(launch_reset(v_, fs_init_, rho_init_, v_.ctrl, stream_), "k_reset")) return PVIO_ERR_HIP;
-    std::memset(h_ctrl_, 0, sizeof(Ctrl));
-    h_ctrl_->mode = MODE_INIT;
-    h_ctrl_->mu = 0.0; // no damping: the Schur weight of a landmark is 1 / H_ll
-    if (check(hipMemcpyAsync(v_.ctrl, h_ctrl_, sizeof(Ctrl), hipMemcpyHostToDevice, stream_), "ctrl")) return PVIO_ERR_HIP;
-    hipError_t e;
-    if ((e = launch_linearize(v_, stream_)) != hipSuccess) return check(e, "k_linearize");
-    if ((e = launch_reduce(v_, stream_, 0)) != hipSuccess) return check(e, "k_reduce");
-
     // every coordinate that can be free: the pose of a frame that is not fixed, the motion blocks of a 15-dimensional system
     size_t max_coords = 0;
     for (size_t f = 0; f < N; ++f) max_coords += (pb->frame_fixed[f] ? 0 : 6) + (dm.d == 15 ? 9 : 0);
-    // results: header | coord_free | frame_cov | lm_var | joint_cov (last: copied back only when the caller wants it)
-    const size_t o_free = 2, o_frame = o_free + (D + 7) / 8, o_lm = o_frame + N * 225, o_joint = o_lm + ((M + 7) & ~(size_t)7), n_res = o_joint + D * D;
-    // work: S | scale | tiles | sig6 | row_nz, free_coord (int32)
-    const size_t w_scale = D * D, w_tiles = w_scale + D, w_sig6 = w_tiles + cov_tile_doubles(max_coords), w_int = w_sig6 + 36 * N * N, n_work = w_int + D;
+    const CovSlabs lay(N, M, max_coords);
     double *d_res = nullptr, *d_work = nullptr;
-    {
-        bool grew = false;
-        if (!dev(pool_, "cov_result", n_res, &d_res, &grew) || !dev(pool_, "cov_work", n_work, &d_work, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "covariance buffers");
-    }
-    const size_t n_back = out->joint_cov ? n_res : o_joint;
+    bool grew = false;
+    if (!dev(pool_, "cov_result", lay.n_res, &d_res, &grew) || !dev(pool_, "cov_work", lay.n_work, &d_work, &grew)) return fail(PVIO_ERR_OUT_OF_MEMORY, "covariance buffers");
+    const size_t n_back = out->joint_cov ? lay.n_res : lay.o_joint;
     double *const h_back = static_cast<double *>(h_cov_.reserve(n_back * sizeof(double), (n_back + n_back / 2) * sizeof(double)));
     if (!h_back) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
-    CovArgs a{};
-    a.D = (int32_t)D, a.max_coords = (int32_t)max_coords;
-    a.Sfull = d_work, a.scale = d_work + w_scale, a.tiles = d_work + w_tiles, a.sig6 = d_work + w_sig6;
-    a.row_nz = reinterpret_cast<int32_t *>(d_work + w_int), a.free_coord = a.row_nz + D;
-    a.hdr = reinterpret_cast<CovHdr *>(d_res), a.coord_free = reinterpret_cast<uint8_t *>(d_res + o_free);
-    a.frame_cov = d_res + o_frame, a.lm_var = d_res + o_lm, a.joint_cov = d_res + o_joint;
+    const CovArgs a = lay.args(d_res, d_work);
     // coordinates that are not free have zero rows and columns in every output: the kernels write the free part only
-    if (check(hipMemsetAsync(d_res, 0, n_res * sizeof(double), stream_), "memset")) return PVIO_ERR_HIP;
+    if (check(hipMemsetAsync(d_res, 0, lay.n_res * sizeof(double), stream_), "memset")) return PVIO_ERR_HIP;
     if (check(hipMemsetAsync(a.sig6, 0, 36 * N * N * sizeof(double), stream_), "memset")) return PVIO_ERR_HIP;
     if (timing)
         for (hipEvent_t &ev : cov_ev_)
             if (!ev && check(hipEventCreate(&ev), "hipEventCreate")) return PVIO_ERR_HIP;
+    hipError_t e;
     if (timing) (void)hipEventRecord(cov_ev_[0], stream_);
     if ((e = launch_cov_assemble(v_, a, stream_)) != hipSuccess) return check(e, "k_cov_assemble");
     if (timing) (void)hipEventRecord(cov_ev_[1], stream_);
@@ -1315,7 +1258,6 @@ int BASolver::covariance(const pvio_ba_problem *pb, const pvio_ba_state *st, pvi
     if (check(hipMemcpyAsync(h_back, d_res, n_back * sizeof(double), hipMemcpyDeviceToHost, stream_), "D2H")) return PVIO_ERR_HIP;
     if (check(hipStreamSynchronize(stream_), "covariance sync")) return PVIO_ERR_HIP;
     stage_in_flight_ = false;
-    uploaded_ = false; // the device buffers now hold an undamped linearization, not a solvable window
     if (timing)
         for (int k = 0; k < 3; ++k) {
             float ms = 0.0f;
@@ -1327,10 +1269,10 @@ int BASolver::covariance(const pvio_ba_problem *pb, const pvio_ba_state *st, pvi
     out->positive_definite = hdr->positive_definite;
     out->first_bad_coord = hdr->positive_definite ? -1 : hdr->first_bad_coord;
     if (!hdr->positive_definite) return PVIO_OK; // an unobservable window is an answer, not an error: nothing else is written
-    std::memcpy(out->frame_cov, h_back + o_frame, N * 225 * sizeof(double));
-    if (out->joint_cov) std::memcpy(out->joint_cov, h_back + o_joint, D * D * sizeof(double));
-    if (out->lm_var) std::memcpy(out->lm_var, h_back + o_lm, M * sizeof(double));
-    if (out->coord_free) std::memcpy(out->coord_free, h_back + o_free, D);
+    std::memcpy(out->frame_cov, h_back + lay.o_frame, N * 225 * sizeof(double));
+    if (out->joint_cov) std::memcpy(out->joint_cov, h_back + lay.o_joint, D * D * sizeof(double));
+    if (out->lm_var) std::memcpy(out->lm_var, h_back + lay.o_lm, M * sizeof(double));
+    if (out->coord_free) std::memcpy(out->coord_free, h_back + lay.o_free, D);
     return PVIO_OK;
 }
 
@@ -1340,3 +1282,4 @@ int BASolver::covariance(const pvio_ba_problem *pb, const pvio_ba_state *st, pvi
 // builds ba_solver.cpp -- the product Makefile, the fiber emulator of tests/hipemu, the variant builds of tests/micro -- has them without a
 // change to its list of sources.
 #include "ba_cov.hip"
+

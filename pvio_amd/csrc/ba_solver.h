@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -36,6 +37,8 @@ class DevicePool { // grow-only device allocations keyed by name
 
 struct UploadPlan; // what an upload derives on the host
 struct UploadWork; // the View an upload is building
+struct SolvePack;  // layout of a solve's packed read-back
+struct MargGather; // layout of a marginalization's gathered read-back
 
 class BASolver {
   public:
@@ -66,6 +69,18 @@ class BASolver {
     int run_slots(int n_slots);
     int enqueue_slot(hipEvent_t *ev = nullptr);
     void invalidate_graph();
+    // the steps of solve() (ba_solver.cpp)
+    class ProfileScope; // what solve(prof != nullptr) sets up, undone on every way out
+    int request_solve_buffers(const SolvePack &pack, bool read_back, bool want_states, double **d_pack);
+    int reset_for_solve(); // the control block's template (sent when it changes) + k_reset
+    int profiled_slot(hipEvent_t *pev, pvio_ba_kernel_times *prof); // one eager slot, its events -> prof
+    int time_limit_reached(std::chrono::steady_clock::time_point t0, bool *timed_out); // max_solver_time, agreed on by all ranks
+    int fill_summary(pvio_ba_summary *sum, bool want_states, std::chrono::steady_clock::time_point t0);
+    void unpack_results(const SolvePack &pack, pvio_ba_state *read_back) const; // the packed read-back -> the caller's arrays
+    void dump_ctrl(const char *after); // PVIO_HIP_DEBUG_CTRL
+    // shared by marginalize() and covariance()
+    int linearize_once(int mode, int victim); // k_reset, control block, k_linearize, k_reduce on the window just uploaded
+    int read_back_marg(const MargGather &lay, const double **h_back); // k_gather + one D2H copy + synchronize
     // the steps of upload() behind its argument checks (ba_solver.cpp)
     void plan_upload(const pvio_ba_problem *pb, UploadPlan &plan) const;
     int allocate(UploadWork &w);

@@ -82,6 +82,35 @@ def test_emulated_resident_solve_is_repeatable(emu_ctx, oracle):
     assert (outs[0][0] == outs[1][0]).all() and (outs[0][1] == outs[1][1]).all() and outs[0][2] == outs[1][2]
 
 
+def test_emulated_profiled_solve_leaves_no_trace(emu_ctx, oracle):
+    """pvio_hip_ba_profile_resident puts a stamp buffer into the kernels' arguments for one solve; the ordinary solves behind it are those of a
+    context that never profiled, bit for bit, and run as replays of a slot graph captured without it"""
+    from pvio_amd import BAState, BASummary
+    pb = ba_compare.make(oracle, n_frames=3, n_landmarks=16, use_inertial=True, visibility=3)
+
+    def ordinary(ctx):
+        sm = BASummary(pb)
+        ctx.solve_resident(sm)
+        st = ctx.download(BAState(pb))
+        summary = [sm.termination, sm.is_usable, sm.num_iterations, sm.num_successful_steps, sm.initial_cost, sm.final_cost, sm.trace_len]
+        trace = np.array([[t[k] for k in sorted(t)] for t in sm.trace()], np.float64)
+        return [a.tobytes() for a in (st.frame_state, st.lm_inv_depth, sm.trace_states, np.array(summary, np.float64), trace)]
+
+    plain = HipContext(lib=emu_ctx.lib, use_graph=True)
+    plain.upload(pb)
+    want = ordinary(plain)
+    plain.close()
+    ctx = HipContext(lib=emu_ctx.lib, use_graph=True)
+    ctx.upload(pb)
+    times = ctx.profile_resident(BASummary(pb))
+    assert times["k_linearize"][1] > 0
+    for k in range(2):
+        replays = ctx.graph_replays()
+        assert ordinary(ctx) == want, k
+        assert ctx.graph_replays() == replays + 1, k
+    ctx.close()
+
+
 INVALID, UNSUPPORTED = -1, -5  # PVIO_ERR_INVALID_ARGUMENT, PVIO_ERR_UNSUPPORTED (include/pvio_hip.h)
 
 

@@ -234,6 +234,33 @@ def test_gpu_marg_edge(gpu_roles, oracle, name):
     print(name, run_case(gpu_roles, oracle, name))
 
 
+def _failed_marginalization_leaves_no_window(ctx):
+    """A marginalization that fails behind its upload ("singular victim block": a vision-only window without a prior has no information on the
+    victim's velocity and biases) has used the uploaded window up like one that succeeds: a resident solve answers "no problem uploaded" instead
+    of solving the marginalization's window, and a fresh upload solves as before."""
+    from pvio_amd.solver import HipError
+    pb = synth.make_window(n_frames=2, n_landmarks=8, use_inertial=False, visibility=2)
+    assert pb.n_obs == 8 and len(pb.prior_frames) == 0
+    st = ctx.upload(pb)
+    first = ctx.solve_resident(BASummary(pb, trace=False))
+    with pytest.raises(HipError, match=r"status -1 \(singular victim block\)"):
+        ctx.marginalize(pb, st, 0)
+    with pytest.raises(HipError, match=r"status -1 \(no problem uploaded\)"):  # PVIO_ERR_INVALID_ARGUMENT
+        ctx.solve_resident(BASummary(pb, trace=False))
+    ctx.upload(pb)
+    again = ctx.solve_resident(BASummary(pb, trace=False))
+    assert again.num_iterations == first.num_iterations and again.final_cost == first.final_cost
+
+
+def test_emulated_failed_marginalization_leaves_no_window(emu_roles):
+    _failed_marginalization_leaves_no_window(emu_roles[1])
+
+
+@pytest.mark.gpu
+def test_gpu_failed_marginalization_leaves_no_window(gpu_roles):
+    _failed_marginalization_leaves_no_window(gpu_roles[0])
+
+
 @pytest.mark.gpu
 def test_gpu_marg_large_window_roles_agree(gpu_roles, oracle):
     """10 KF x 50 000 landmarks (bench.py's large-window row), marginalized at the initial state: both roles, and the oracle"""
