@@ -291,6 +291,42 @@ int32_t pvio_hip_ba_covariance(pvio_hip_ctx *ctx, const pvio_ba_problem *problem
  * recorded only when PVIO_HIP_TIMING is set in the environment (zeros otherwise) */
 int32_t pvio_hip_ba_covariance_kernel_ms(const pvio_hip_ctx *ctx, double ms[3]);
 
+/* Batched multi-view DLT triangulation: poses and observations -> landmarks, one kernel launch for all tracks of the call.
+ * Reference: Track::triangulate / try_triangulate (map/track.cpp:61-106) + triangulate_point_scored (geometry/stereo.h:67-74,104-128).
+ *   system    rows u P_2 - P_0 and v P_2 - P_1 of each of the track's K observations (z = (u, v), P = view_P of its view): 2K x 4
+ *   q         the right singular vector of the smallest singular value of that matrix (one-sided Jacobi on the rows, no A^T A), |q| = 1,
+ *             sign fixed so that q[3] >= 0; if q[3] == 0 the first non-zero of q[0..2] is positive.  (The reference leaves the sign to
+ *             Eigen; it only shows in `point` of a failed track.)
+ *   ok        with y_i = P_i q: 0 as soon as any observation has !(y_i[2] q[3] > 0) or !(y_i[2] / q[3] < 100) -- the negated comparisons
+ *             of the reference, so NaN gives 0 (`has_parallax` of stereo.h:104-128)
+ *   point     q[0..2] / q[3] when ok, else q[0..2] / |q[0..2]|
+ *   score     sum_i |y_i[0..1] / y_i[2] - z_i|^2 / K, for every track, ok or not; may be non-finite when a y_i[2] is 0
+ * The reference's two-view overload (stereo.h:86-102) is the same computation; it differs only in leaving p untouched and score = 0 on failure.
+ * A track with fewer than 2 observations gets ok = 0, point = 0, score = +inf, q = 0 (the reference asserts there).
+ * PVIO_ERR_INVALID_ARGUMENT, with nothing written: NULL point or ok; NULL inputs with n_tracks > 0; n_views < 1 or n_tracks < 0; track_ptr not
+ * starting at 0 or decreasing; a track with more than PVIO_TRI_MAX_OBS observations; an obs_view outside [0, n_views).  n_tracks == 0
+ * returns PVIO_OK.
+ * The call owns its buffers: a window uploaded with pvio_hip_ba_upload stays uploaded and the next pvio_hip_ba_solve_resident returns the
+ * same bits as without the call.  It does not touch the communicator.  Two calls on the same input return the same bits. */
+#define PVIO_TRI_MAX_OBS 32            /* = PVIO_MAX_FRAMES: observations of one track */
+typedef struct pvio_tri_problem {
+    int32_t n_views, n_tracks;         /* V >= 1, T >= 0 */
+    const double *view_P;              /* [V][12] 3x4 row-major [R | t] onto NORMALIZED image coordinates (track.cpp:66-73: R = R_wc^T, t = -R p_wc) */
+    const int32_t *track_ptr;          /* [T+1] CSR, track_ptr[0] = 0, non-decreasing */
+    const int32_t *obs_view;           /* [..] view index of each observation, any order inside a track */
+    const double *obs_z;               /* [..][2] normalized keypoints */
+} pvio_tri_problem;
+typedef struct pvio_tri_result {
+    double *point;                     /* [T][3] */
+    uint8_t *ok;                       /* [T]    has_parallax of stereo.h:104-128 */
+    double *score;                     /* optional [T] */
+    double *homogeneous;               /* optional [T][4] the unit null vector q */
+} pvio_tri_result;
+int32_t pvio_hip_triangulate(pvio_hip_ctx *ctx, const pvio_tri_problem *problem, pvio_tri_result *out);
+/* diagnostics of the last pvio_hip_triangulate of this context: the largest number of Jacobi sweeps a track took (the kernel's bound is 30),
+ * and the hipEvent time of the kernel in ms -- recorded only when PVIO_HIP_TIMING is set in the environment, else 0 */
+int32_t pvio_hip_triangulate_stats(const pvio_hip_ctx *ctx, int32_t *max_sweeps, double *kernel_ms);
+
 /* multi-GPU (landmark shards, one process per GPU): RCCL communicator bootstrap.
  * rank 0 creates the 128-byte unique id, the launcher broadcasts it (torch.distributed), every rank inits. */
 int32_t pvio_hip_comm_unique_id(uint8_t id[128]);

@@ -78,6 +78,18 @@ class BACovarianceC(C.Structure):
 COV_MIN_PIVOT = 1e-10  # PVIO_COV_MIN_PIVOT
 
 
+class TriProblemC(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("n_tracks", C.c_int32), ("view_P", c_double_p), ("track_ptr", c_int32_p), ("obs_view", c_int32_p),
+                ("obs_z", c_double_p)]
+
+
+class TriResultC(C.Structure):
+    _fields_ = [("point", c_double_p), ("ok", c_uint8_p), ("score", c_double_p), ("homogeneous", c_double_p)]
+
+
+TRI_MAX_OBS = 32  # PVIO_TRI_MAX_OBS
+
+
 class BAKernelTimesC(C.Structure):
     _fields_ = [("total_ms", C.c_double * 4), ("launches", C.c_int32 * 4), ("phase_ticks", (C.c_int64 * 32) * 4),
                 ("comm_ms", C.c_double * 2), ("comm_launches", C.c_int32 * 2)]
@@ -94,6 +106,7 @@ ABI_VERSION = 2  # PVIO_HIP_ABI_VERSION of include/pvio_hip.h these ctypes struc
 EXPORTS = [
     "pvio_hip_create", "pvio_hip_destroy", "pvio_hip_last_error", "pvio_hip_version", "pvio_hip_abi_version",
     "pvio_hip_ba_solve", "pvio_hip_ba_marginalize", "pvio_hip_ba_reprojection_error", "pvio_hip_ba_covariance", "pvio_hip_ba_covariance_kernel_ms",
+    "pvio_hip_triangulate", "pvio_hip_triangulate_stats",
     "pvio_hip_ba_upload", "pvio_hip_ba_solve_resident", "pvio_hip_ba_download", "pvio_hip_ba_profile_resident", "pvio_hip_ba_last_candidate_repeats", "pvio_hip_ba_graph_replays",
     "pvio_hip_comm_unique_id", "pvio_hip_comm_init", "pvio_preintegrate",
     "pvio_hip_image_create", "pvio_hip_image_release", "pvio_hip_image_download_level", "pvio_hip_klt_track", "pvio_hip_image_detect", "pvio_hip_image_download_response",
@@ -136,6 +149,10 @@ def load(path=None):
     lib.pvio_hip_ba_covariance.restype = C.c_int32
     lib.pvio_hip_ba_covariance_kernel_ms.argtypes = [vp, c_double_p]
     lib.pvio_hip_ba_covariance_kernel_ms.restype = C.c_int32
+    lib.pvio_hip_triangulate.argtypes = [vp, C.POINTER(TriProblemC), C.POINTER(TriResultC)]
+    lib.pvio_hip_triangulate.restype = C.c_int32
+    lib.pvio_hip_triangulate_stats.argtypes = [vp, c_int32_p, c_double_p]
+    lib.pvio_hip_triangulate_stats.restype = C.c_int32
     lib.pvio_hip_ba_reprojection_error.argtypes = [vp, C.POINTER(BAProblemC), C.POINTER(BAStateC), c_double_p]
     lib.pvio_hip_ba_reprojection_error.restype = C.c_int32
     lib.pvio_hip_ba_upload.argtypes = [vp, C.POINTER(BAProblemC), C.POINTER(BAStateC)]

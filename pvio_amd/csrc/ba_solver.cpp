@@ -7,7 +7,7 @@
 //
 // In order: upload in its five steps; the read-back layouts (SolvePack, MargGather, CovSlabs); solve in its steps (enqueue_slot, run_slots,
 // request_solve_buffers, reset_for_solve, ProfileScope, profiled_slot, time_limit_reached, fill_summary, unpack_results); the one-shot calls
-// marginalize and covariance above linearize_once.  The marginalization's dense host algebra is marg_prior.h.
+// marginalize and covariance above linearize_once; triangulate in its steps.  The marginalization's dense host algebra is marg_prior.h.
 #include "ba_solver.h"
 
 #include <algorithm>
@@ -17,6 +17,7 @@
 
 #include "ba_cov.h"
 #include "ba_kernels.h"
+#include "ba_triangulate.h"
 #include "marg_prior.h"
 
 namespace pvba {
@@ -72,6 +73,8 @@ BASolver::~BASolver() {
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
     for (hipEvent_t ev : cov_ev_)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : tri_ev_)
         if (ev) (void)hipEventDestroy(ev);
     if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -1276,10 +1279,120 @@ int BASolver::covariance(const pvio_ba_problem *pb, const pvio_ba_state *st, pvi
     return PVIO_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// triangulate = validate -> stage -> launch -> fetch (pvio_hip_triangulate).  One buffer on the device and its pinned twin on the host, both
+// the call's own and kept between calls: neither the pool nor the View of an uploaded window is touched.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// a triangulation call's buffer, in doubles: view_P | obs_z | track_ptr | obs_view | header | results.  The upload is [0, o_res) -- the header
+// goes up as zeros --, the read-back is [o_hdr, n_total).
+struct TriLayout {
+    size_t V = 0, T = 0, n_obs = 0, o_z = 0, o_ptr = 0, o_view = 0, o_hdr = 0, o_res = 0, n_total = 0;
+    int max_obs = 0; // the longest track of the call
+    void set(size_t V_, size_t T_, size_t n_obs_, int max_obs_) {
+        V = V_, T = T_, n_obs = n_obs_, max_obs = max_obs_;
+        o_z = 12 * V, o_ptr = o_z + 2 * n_obs, o_view = o_ptr + (T + 2) / 2, o_hdr = o_view + (n_obs + 1) / 2, o_res = o_hdr + 1, n_total = o_res + kTriRecord * T;
+    }
+    TriArgs args(double *d) const {
+        TriArgs a{};
+        a.n_tracks = (int32_t)T;
+        a.view_P = d, a.obs_z = d + o_z;
+        a.track_ptr = reinterpret_cast<const int32_t *>(d + o_ptr), a.obs_view = reinterpret_cast<const int32_t *>(d + o_view);
+        a.max_sweeps = reinterpret_cast<int32_t *>(d + o_hdr), a.result = d + o_res;
+        return a;
+    }
+};
+
+// every rejection of include/pvio_hip.h, before anything is written anywhere
+int BASolver::validate_tracks(const pvio_tri_problem *pb, const pvio_tri_result *out, TriLayout &lay) {
+    if (!pb || !out || !out->point || !out->ok) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_triangulate: null argument (point and ok are not optional)");
+    if (pb->n_views < 1 || pb->n_tracks < 0) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_triangulate: n_views < 1 or n_tracks < 0");
+    const size_t T = (size_t)pb->n_tracks;
+    if (T == 0) {
+        lay.set((size_t)pb->n_views, 0, 0, 0);
+        return PVIO_OK;
+    }
+    if (!pb->view_P || !pb->track_ptr) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_triangulate: null view_P or track_ptr");
+    if (pb->track_ptr[0] != 0) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_triangulate: track_ptr[0] != 0");
+    int max_obs = 0;
+    for (size_t t = 0; t < T; ++t) {
+        const int64_t k = (int64_t)pb->track_ptr[t + 1] - (int64_t)pb->track_ptr[t];
+        if (k < 0) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_triangulate: track_ptr decreases at track " + std::to_string(t));
+        if (k > PVIO_TRI_MAX_OBS) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_triangulate: track " + std::to_string(t) + " has more than PVIO_TRI_MAX_OBS observations");
+        max_obs = std::max(max_obs, (int)k);
+    }
+    const size_t n_obs = (size_t)pb->track_ptr[T];
+    if (n_obs > 0 && (!pb->obs_view || !pb->obs_z)) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_triangulate: null obs_view or obs_z");
+    for (size_t o = 0; o < n_obs; ++o)
+        if (pb->obs_view[o] < 0 || pb->obs_view[o] >= pb->n_views) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_triangulate: obs_view[" + std::to_string(o) + "] is outside [0, n_views)");
+    lay.set((size_t)pb->n_views, T, n_obs, max_obs);
+    return PVIO_OK;
+}
+
+// the inputs into the pinned twin, then ONE copy to the device
+int BASolver::stage_tracks(const pvio_tri_problem *pb, const TriLayout &lay) {
+    const size_t bytes = lay.n_total * sizeof(double);
+    if (!d_tri_.reserve(bytes, bytes + bytes / 2)) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipMalloc failed (triangulation buffer)");
+    double *const h = static_cast<double *>(h_tri_.reserve(bytes, bytes + bytes / 2));
+    if (!h) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed (triangulation buffer)");
+    std::memcpy(h, pb->view_P, 12 * lay.V * sizeof(double));
+    if (lay.n_obs) std::memcpy(h + lay.o_z, pb->obs_z, 2 * lay.n_obs * sizeof(double));
+    std::memset(h + lay.o_ptr, 0, (lay.o_res - lay.o_ptr) * sizeof(double)); // the int arrays' padding and the header
+    std::memcpy(h + lay.o_ptr, pb->track_ptr, (lay.T + 1) * sizeof(int32_t));
+    if (lay.n_obs) std::memcpy(h + lay.o_view, pb->obs_view, lay.n_obs * sizeof(int32_t));
+    return check(hipMemcpyAsync(d_tri_.data(), h, lay.o_res * sizeof(double), hipMemcpyHostToDevice, stream_), "triangulate H2D");
+}
+
+int BASolver::launch_tracks(const TriLayout &lay) {
+    const bool timing = solver_switches().timing; // diagnostics: hipEvents around the kernel
+    if (timing)
+        for (hipEvent_t &ev : tri_ev_)
+            if (!ev && check(hipEventCreate(&ev), "hipEventCreate")) return PVIO_ERR_HIP;
+    if (timing) (void)hipEventRecord(tri_ev_[0], stream_);
+    const hipError_t e = launch_triangulate(lay.args(d_tri_.as<double>()), tri_group_lanes(lay.max_obs), stream_);
+    if (e != hipSuccess) return check(e, "k_triangulate");
+    if (timing) (void)hipEventRecord(tri_ev_[1], stream_);
+    return PVIO_OK;
+}
+
+// ONE copy back through the pinned twin, then the records into the caller's arrays
+int BASolver::fetch_tracks(const TriLayout &lay, pvio_tri_result *out) {
+    double *const h = h_tri_.as<double>();
+    if (check(hipMemcpyAsync(h + lay.o_hdr, d_tri_.as<double>() + lay.o_hdr, (lay.n_total - lay.o_hdr) * sizeof(double), hipMemcpyDeviceToHost, stream_), "triangulate D2H")) return PVIO_ERR_HIP;
+    if (check(hipStreamSynchronize(stream_), "triangulate sync")) return PVIO_ERR_HIP;
+    stage_in_flight_ = false; // whatever an upload left queued on the stream has been read as well
+    if (solver_switches().timing) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, tri_ev_[0], tri_ev_[1]);
+        tri_ms_ = ms;
+    }
+    tri_sweeps_ = *reinterpret_cast<const int32_t *>(h + lay.o_hdr);
+    for (size_t t = 0; t < lay.T; ++t) {
+        const double *rec = h + lay.o_res + kTriRecord * t;
+        if (out->homogeneous) std::memcpy(out->homogeneous + 4 * t, rec, 4 * sizeof(double));
+        std::memcpy(out->point + 3 * t, rec + 4, 3 * sizeof(double));
+        if (out->score) out->score[t] = rec[7];
+        out->ok[t] = rec[8] != 0.0 ? 1 : 0;
+    }
+    return PVIO_OK;
+}
+
+int BASolver::triangulate(const pvio_tri_problem *pb, pvio_tri_result *out) {
+    TriLayout lay;
+    int rc = validate_tracks(pb, out, lay);
+    if (rc != PVIO_OK) return rc;
+    tri_sweeps_ = 0, tri_ms_ = 0.0;
+    if (lay.T == 0) return PVIO_OK;
+    if ((rc = stage_tracks(pb, lay)) != PVIO_OK) return rc;
+    if ((rc = launch_tracks(lay)) != PVIO_OK) return rc;
+    return fetch_tracks(lay, out);
+}
+
 } // namespace pvba
 
 // The kernels of covariance() and their launchers.  They are compiled as part of this translation unit, not as an object of their own: whatever
 // builds ba_solver.cpp -- the product Makefile, the fiber emulator of tests/hipemu, the variant builds of tests/micro -- has them without a
 // change to its list of sources.
 #include "ba_cov.hip"
-
+// The kernel of triangulate() and its launcher, for the same reason.
+#include "ba_triangulate.hip"

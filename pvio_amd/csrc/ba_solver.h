@@ -39,6 +39,7 @@ struct UploadPlan; // what an upload derives on the host
 struct UploadWork; // the View an upload is building
 struct SolvePack;  // layout of a solve's packed read-back
 struct MargGather; // layout of a marginalization's gathered read-back
+struct TriLayout;  // layout of a triangulation call's device buffer
 
 class BASolver {
   public:
@@ -59,6 +60,9 @@ class BASolver {
     int marginalize(const pvio_ba_problem *pb, const pvio_ba_state *st, int victim, pvio_ba_prior *out);
     int covariance(const pvio_ba_problem *pb, const pvio_ba_state *st, pvio_ba_covariance *out); // marginal covariances of the window (ba_cov.hip)
     const double *last_covariance_kernel_ms() const { return cov_ms_; } // k_cov_assemble, k_cov_invert, k_cov_landmarks of the last call (PVIO_HIP_TIMING)
+    int triangulate(const pvio_tri_problem *pb, pvio_tri_result *out); // batched DLT triangulation (ba_triangulate.hip); leaves an uploaded window alone
+    int last_triangulate_sweeps() const { return tri_sweeps_; }        // most Jacobi sweeps a track of the last call took
+    double last_triangulate_kernel_ms() const { return tri_ms_; }      // k_triangulate of the last call (PVIO_HIP_TIMING)
     void set_comm(Comm *c) { comm_ = c; }
     const std::string &error() const { return err_; }
     hipStream_t stream() const { return stream_; }
@@ -81,6 +85,11 @@ class BASolver {
     // shared by marginalize() and covariance()
     int linearize_once(int mode, int victim); // k_reset, control block, k_linearize, k_reduce on the window just uploaded
     int read_back_marg(const MargGather &lay, const double **h_back); // k_gather + one D2H copy + synchronize
+    // the steps of triangulate() (ba_solver.cpp)
+    int validate_tracks(const pvio_tri_problem *pb, const pvio_tri_result *out, TriLayout &lay);
+    int stage_tracks(const pvio_tri_problem *pb, const TriLayout &lay);
+    int launch_tracks(const TriLayout &lay);
+    int fetch_tracks(const TriLayout &lay, pvio_tri_result *out);
     // the steps of upload() behind its argument checks (ba_solver.cpp)
     void plan_upload(const pvio_ba_problem *pb, UploadPlan &plan) const;
     int allocate(UploadWork &w);
@@ -111,6 +120,11 @@ class BASolver {
     pvhip::PinnedBuffer h_cov_;  // pinned read-back of one covariance call
     hipEvent_t cov_ev_[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three kernels of a covariance call, created on first use (PVIO_HIP_TIMING)
     double cov_ms_[3] = {0.0, 0.0, 0.0};
+    pvhip::DeviceBuffer d_tri_;  // a triangulation call's inputs and results (its own: the window's buffers are not touched)
+    pvhip::PinnedBuffer h_tri_;  // pinned staging of those inputs and read-back of those results
+    hipEvent_t tri_ev_[2] = {nullptr, nullptr}; // around k_triangulate, created on first use (PVIO_HIP_TIMING)
+    int tri_sweeps_ = 0;
+    double tri_ms_ = 0.0;
     pvhip::PinnedBuffer h_pack_; // pinned: a solve's packed results (k_quality `pack`, doubles)
     const double *fs_init_ = nullptr, *rho_init_ = nullptr; // initial state inside the inputs slab
     Ctrl h_ctrl_tmpl_{};                                    // what a solve's control block starts from (k_reset copies the device copy)

@@ -109,6 +109,16 @@ int32_t pvio_hip_ba_covariance_kernel_ms(const pvio_hip_ctx *ctx, double ms[3]) 
     for (int k = 0; k < 3; ++k) ms[k] = ctx->ba->last_covariance_kernel_ms()[k];
     return PVIO_OK;
 }
+int32_t pvio_hip_triangulate(pvio_hip_ctx *ctx, const pvio_tri_problem *problem, pvio_tri_result *out) {
+    if (!ctx || !ctx->ba) return PVIO_ERR_INVALID_ARGUMENT;
+    return ctx->ba->triangulate(problem, out); // (its argument checks leave a message for pvio_hip_last_error)
+}
+int32_t pvio_hip_triangulate_stats(const pvio_hip_ctx *ctx, int32_t *max_sweeps, double *kernel_ms) {
+    if (!ctx || !ctx->ba) return PVIO_ERR_INVALID_ARGUMENT;
+    if (max_sweeps) *max_sweeps = ctx->ba->last_triangulate_sweeps();
+    if (kernel_ms) *kernel_ms = ctx->ba->last_triangulate_kernel_ms();
+    return PVIO_OK;
+}
 int32_t pvio_hip_ba_reprojection_error(pvio_hip_ctx *ctx, const pvio_ba_problem *problem, const pvio_ba_state *state, double *mean_pixel_error) {
     if (!ctx || !problem || !state || !mean_pixel_error) return PVIO_ERR_INVALID_ARGUMENT;
     int rc = ctx->ba->upload(problem, state);

@@ -30,6 +30,9 @@
 
 #include "../../include/pvio_hip.h"
 
+// (see device_triangulation() below)
+extern "C" int32_t pvio_hip_triangulate(pvio_hip_ctx *ctx, const pvio_tri_problem *problem, pvio_tri_result *out) __attribute__((weak));
+
 namespace pvio {
 
 namespace {
@@ -454,17 +457,106 @@ bool track_quality(const Track *track, double &quality) {
     return true;
 }
 
+// PVIO_HIP_DEVICE_TRIANGULATION=1 (read once; default off): the re-validation below triangulates its tracks in one pvio_hip_triangulate call
+// in place of one host SVD per track (Track::try_triangulate).  The reference to that entry point is weak (below, outside the namespaces): it
+// was added without a change of PVIO_HIP_ABI_VERSION, so a back end of the same ABI version may not have it (an older libpvio_hip.so; the
+// oracle-backed C ABI of the parity chain), and an option that is off by default must not keep the adapter from loading above one.  Asking for
+// the device path above such a back end is reported once and the host path is taken.
+bool device_triangulation() {
+    static const bool on = [] {
+        const char *v = std::getenv("PVIO_HIP_DEVICE_TRIANGULATION");
+        if (!(v && std::atoi(v) != 0)) return false;
+        if (!pvio_hip_triangulate) {
+            std::fprintf(stderr, "[pvio-hip] PVIO_HIP_DEVICE_TRIANGULATION: this back end has no pvio_hip_triangulate, the plane tracks are triangulated on the host\n");
+            return false;
+        }
+        return true;
+    }();
+    return on;
+}
+
+// Track::try_triangulate (track.cpp:61-80) for all of `tracks` at once: view_P = [R | -R p], R = R_wc^T, of every frame's current camera pose,
+// one pvio_hip_triangulate call.  ok[i] / point[i] are what try_triangulate returns / writes.  A track the call does not take (more than
+// PVIO_TRI_MAX_OBS observations, a frame outside the map) is marked in `on_host` and left to try_triangulate; false: the call itself failed.
+bool triangulate_on_device(pvio_hip_ctx *ctx, Map *map, const std::vector<Track *> &tracks, std::vector<uint8_t> &ok, std::vector<double> &point, std::vector<uint8_t> &on_host) {
+    static thread_local std::vector<double> view_P, obs_z;
+    static thread_local std::vector<int32_t> track_ptr, obs_view;
+    static thread_local FrameIndex index;
+    const size_t V = map->frame_num();
+    index.clear();
+    view_P.resize(12 * V);
+    for (size_t i = 0; i < V; ++i) {
+        const Frame *frame = map->get_frame(i);
+        index.put(frame, (int)i);
+        const PoseState cam = frame->get_pose(frame->camera);
+        const double x = cam.q.coeffs()[0], y = cam.q.coeffs()[1], z = cam.q.coeffs()[2], w = cam.q.coeffs()[3];
+        const double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)},  // R_wc
+                                {2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)},
+                                {2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)}};
+        double *P = &view_P[12 * i];
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) P[4 * r + c] = R[c][r];
+            P[4 * r + 3] = -(R[0][r] * cam.p[0] + R[1][r] * cam.p[1] + R[2][r] * cam.p[2]);
+        }
+    }
+    const size_t T = tracks.size();
+    track_ptr.assign(1, 0), obs_view.clear(), obs_z.clear();
+    on_host.assign(T, 0);
+    for (size_t i = 0; i < T; ++i) {
+        const size_t first = obs_view.size();
+        if (tracks[i]->keypoint_num() > PVIO_TRI_MAX_OBS) on_host[i] = 1;
+        else
+            for (const auto &fk : tracks[i]->keypoint_map()) {
+                const int v = index.find(fk.first);
+                if (v < 0) {
+                    on_host[i] = 1;
+                    break;
+                }
+                const vector<2> &kp = fk.first->get_keypoint(fk.second);
+                obs_view.push_back(v), obs_z.push_back(kp[0]), obs_z.push_back(kp[1]);
+            }
+        if (on_host[i]) obs_view.resize(first), obs_z.resize(2 * first); // an empty track: the device reports ok = 0, the caller does not look
+        track_ptr.push_back((int32_t)obs_view.size());
+    }
+    ok.assign(T, 0), point.assign(3 * T, 0.0);
+    pvio_tri_problem pb{(int32_t)V, (int32_t)T, view_P.data(), track_ptr.data(), obs_view.data(), obs_z.data()};
+    pvio_tri_result out{point.data(), ok.data(), nullptr, nullptr};
+    if (pvio_hip_triangulate(ctx, &pb, &out) != PVIO_OK) {
+        std::fprintf(stderr, "[pvio-hip] triangulate failed: %s (the plane tracks are triangulated on the host)\n", pvio_hip_last_error(ctx));
+        return false;
+    }
+    return true;
+}
+
 // :251-275 -- PLANE tracks that can be triangulated on their own are checked against the planes they sit in (0.1 m): a
 // plane that does not hold the point loses the track, a track that no plane holds goes back to being an ordinary VALID
-// landmark at the triangulated point.  Returns the tracks whose inverse depth it replaced.
-std::vector<Track *> revalidate_plane_tracks(Map *map) {
+// landmark at the triangulated point.  Returns the tracks whose inverse depth it replaced.  The triangulations are one host SVD per track
+// (Track::try_triangulate) or, with device_triangulation(), one call for all of them; the gate and what follows it are the same code.
+std::vector<Track *> revalidate_plane_tracks(Map *map, pvio_hip_ctx *ctx, size_t *on_device_count) {
     std::vector<Track *> moved;
+    static thread_local std::vector<Track *> candidates;
+    static thread_local std::vector<uint8_t> ok, on_host;
+    static thread_local std::vector<double> point;
+    candidates.clear();
     for (size_t i = 0; i < map->track_num(); ++i) {
         Track *track = map->get_track(i);
         if (!track->flag(TrackFlag::TF_PLANE)) continue;
         if (track->keypoint_num() < 2) continue;
+        if (!(track->life > 10 && PlaneExtractor::enough_baseline(track))) continue;
+        candidates.push_back(track);
+    }
+    const bool device = device_triangulation() && ctx && !candidates.empty() && triangulate_on_device(ctx, map, candidates, ok, point, on_host);
+    *on_device_count = 0;
+    for (size_t i = 0; i < candidates.size(); ++i) {
+        Track *track = candidates[i];
         vector<3> p;
-        if (!(track->life > 10 && PlaneExtractor::enough_baseline(track) && track->try_triangulate(p))) continue;
+        if (device && !on_host[i]) {
+            ++*on_device_count;
+            if (!ok[i]) continue;
+            for (int k = 0; k < 3; ++k) p[k] = point[3 * i + k];
+        } else if (!track->try_triangulate(p)) {
+            continue;
+        }
         bool held = false;
         for (size_t j = 0; j < map->plane_num(); ++j) {
             Plane *plane = map->get_plane(j);
@@ -563,7 +655,10 @@ struct BundleAdjustor::BundleAdjustorSolver { // the pimpl of bundle_adjustor.h:
         // ---- post-solve passes (:251-296).  The depth gate and the mean pixel error of the flattened landmarks come from the
         // device (k_quality, evaluated on the final states); the plane-track re-validation and the tracks the device never
         // saw (PLANE tracks of planes with >= 20 tracks, tracks the re-validation has just moved) are done here. ----
-        const std::vector<Track *> moved = revalidate_plane_tracks(map);
+        const auto t_reval = std::chrono::steady_clock::now();
+        size_t reval_on_device = 0;
+        const std::vector<Track *> moved = revalidate_plane_tracks(map, ctx, &reval_on_device);
+        const double reval_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_reval).count();
         static thread_local PtrSet on_device;
         on_device.reset(F.lm_track.size());
         for (size_t l = 0; l < F.lm_track.size(); ++l) {
@@ -587,6 +682,8 @@ struct BundleAdjustor::BundleAdjustorSolver { // the pimpl of bundle_adjustor.h:
             auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
             std::fprintf(stderr, "[pvio-hip] solve: %d frames, %d landmarks, %d factors: flatten %.1f us, upload+solve+download %.1f us (device %.1f us, %d iterations), write-back + post passes %.1f us\n",
                          F.pb.n_frames, F.pb.n_landmarks, F.pb.n_obs, us(t0, t1), us(t1, t2), 1e6 * sum.device_seconds, sum.num_iterations, us(t2, t3));
+            std::fprintf(stderr, "[pvio-hip] plane re-validation: %.1f us, %zu tracks triangulated on the device, %zu tracks moved (PVIO_HIP_DEVICE_TRIANGULATION %s)\n",
+                         reval_us, reval_on_device, moved.size(), device_triangulation() ? "on" : "off");
         }
         return sum.is_usable != 0;
     }

@@ -139,6 +139,82 @@ class HipContext:
         self._check(self.lib.pvio_hip_ba_covariance_kernel_ms(self.ctx, ms.ctypes.data_as(capi.c_double_p)), "pvio_hip_ba_covariance_kernel_ms")
         return ms
 
+    def triangulate(self, view_P, track_ptr, obs_view, obs_z, homogeneous=False):
+        """pvio_hip_triangulate: batched multi-view DLT triangulation (include/pvio_hip.h).  view_P [V, 3, 4] (or [V, 12]) onto normalized image
+        coordinates, track_ptr [T + 1] CSR over obs_view [n] / obs_z [n, 2].  Returns a dict: point [T, 3], ok [T] (uint8), score [T] and, on
+        request, homogeneous [T, 4]."""
+        view_P = np.ascontiguousarray(view_P, np.float64).reshape(-1, 12)
+        track_ptr = np.ascontiguousarray(track_ptr, np.int32)
+        obs_view = np.ascontiguousarray(obs_view, np.int32)
+        obs_z = np.ascontiguousarray(obs_z, np.float64).reshape(-1, 2)
+        T = track_ptr.shape[0] - 1
+        res = dict(point=np.zeros((T, 3)), ok=np.zeros(T, np.uint8), score=np.zeros(T))
+        if homogeneous:
+            res["homogeneous"] = np.zeros((T, 4))
+        pb, out = capi.TriProblemC(), capi.TriResultC()
+        pb.n_views, pb.n_tracks = view_P.shape[0], T
+        pb.view_P, pb.obs_z = view_P.ctypes.data_as(capi.c_double_p), obs_z.ctypes.data_as(capi.c_double_p)
+        pb.track_ptr, pb.obs_view = track_ptr.ctypes.data_as(capi.c_int32_p), obs_view.ctypes.data_as(capi.c_int32_p)
+        out.point, out.ok, out.score = res["point"].ctypes.data_as(capi.c_double_p), res["ok"].ctypes.data_as(capi.c_uint8_p), res["score"].ctypes.data_as(capi.c_double_p)
+        if homogeneous:
+            out.homogeneous = res["homogeneous"].ctypes.data_as(capi.c_double_p)
+        self._check(self.lib.pvio_hip_triangulate(self.ctx, C.byref(pb), C.byref(out)), "pvio_hip_triangulate")
+        return res
+
+    def triangulate_stats(self):
+        """(max_sweeps, kernel_ms) of the last triangulate(): the most Jacobi sweeps a track took; the kernel's hipEvent time, recorded only with
+        PVIO_HIP_TIMING set (else 0)"""
+        sweeps, ms = C.c_int32(0), C.c_double(0.0)
+        self._check(self.lib.pvio_hip_triangulate_stats(self.ctx, C.byref(sweeps), C.byref(ms)), "pvio_hip_triangulate_stats")
+        return int(sweeps.value), float(ms.value)
+
+    def triangulate_window(self, problem, state, planes=False):
+        """The landmarks of a flattened window (or, planes=True, its plane tracks) triangulated from the camera poses of `state`.  Views are
+        the frames' cameras (Frame::get_pose(camera): q_c = q_b * q_cs, p_c = p_b + R(q_b) p_cs); a landmark's track is its anchor observation
+        followed by its CSR observations, a plane track is its CSR list.  Adds inv_depth [T] = 1 / (R_a^T (point - p_a)).z in the camera of the
+        track's first observation (Track::set_landmark_point), NaN where ok == 0, and returns the flattening next to the results."""
+        view_P, R_wc, p_wc = window_views(problem, state)
+        track_ptr, obs_view, obs_z = window_tracks(problem, planes)
+        res = self.triangulate(view_P, track_ptr, obs_view, obs_z, homogeneous=True)
+        first = obs_view[track_ptr[:-1]]
+        depth = np.einsum("tk,tk->t", R_wc[first][:, :, 2], res["point"] - p_wc[first])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            res["inv_depth"] = np.where(res["ok"] == 1, 1.0 / depth, np.nan)
+        res.update(view_P=view_P, track_ptr=track_ptr, obs_view=obs_view, obs_z=obs_z)
+        return res
+
+
+def window_views(problem, state):
+    """(view_P [N, 3, 4], R_wc [N, 3, 3], p_wc [N, 3]) of a window's cameras at `state`: P = [R_wc^T | -R_wc^T p_wc] (track.cpp:66-73)"""
+    from .synth import qmat
+    N = problem.n_frames
+    view_P, R_wc, p_wc = np.zeros((N, 3, 4)), np.zeros((N, 3, 3)), np.zeros((N, 3))
+    for f in range(N):
+        R_b = qmat(state.frame_state[f, 0:4] / np.linalg.norm(state.frame_state[f, 0:4]))
+        R_wc[f] = R_b @ qmat(problem.cam_extrinsic[f, 0:4] / np.linalg.norm(problem.cam_extrinsic[f, 0:4]))
+        p_wc[f] = state.frame_state[f, 4:7] + R_b @ problem.cam_extrinsic[f, 4:7]
+        view_P[f, :, :3] = R_wc[f].T
+        view_P[f, :, 3] = -R_wc[f].T @ p_wc[f]
+    return view_P, R_wc, p_wc
+
+
+def window_tracks(problem, planes=False):
+    """(track_ptr, obs_view, obs_z) of a window's landmarks -- anchor observation first -- or of its plane tracks"""
+    if planes:
+        return (np.ascontiguousarray(problem.plane_obs_ptr, np.int32), np.ascontiguousarray(problem.plane_obs_frame, np.int32),
+                np.ascontiguousarray(problem.plane_obs_z, np.float64).reshape(-1, 2))
+    M = problem.n_landmarks
+    lm_ptr = np.asarray(problem.lm_obs_ptr, np.int64)
+    track_ptr = (lm_ptr + np.arange(M + 1)).astype(np.int32)
+    n = int(track_ptr[-1])
+    obs_view, obs_z = np.zeros(n, np.int32), np.zeros((n, 2))
+    anchor_at = track_ptr[:-1].astype(np.int64)
+    is_anchor = np.zeros(n, bool)
+    is_anchor[anchor_at] = True
+    obs_view[anchor_at], obs_z[anchor_at] = problem.lm_anchor_frame[:M], np.asarray(problem.lm_anchor_z).reshape(-1, 2)[:M]
+    obs_view[~is_anchor], obs_z[~is_anchor] = problem.obs_frame[:lm_ptr[M]], np.asarray(problem.obs_z).reshape(-1, 2)[:lm_ptr[M]]
+    return track_ptr, obs_view, obs_z
+
 
 class HipUndistort:
     """Device-resident fixed-point remap tables (pvio_hip_undistort_create): map_xy int16 [h][w][2], map_frac uint16 [h][w]."""
