@@ -1,5 +1,6 @@
 """A complete keyframe solve and marginalization THROUGH THE HOST ADAPTER (pvio::BundleAdjustor of pvio_amd/host: flatten the Map,
-C ABI, write back), with the adapter's and the library's own PVIO_HIP_TIMING lines on stderr.  GPU box: python tests/prof_keyframe.py"""
+C ABI, write back), with the adapter's and the library's own PVIO_HIP_TIMING lines on stderr.
+GPU box: python tests/prof_keyframe.py [path of another libpvio_host.so]"""
 import os, sys
 os.environ["PVIO_HIP_TIMING"] = "1"
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
@@ -8,7 +9,12 @@ import host_compare, marg_compare, ba_compare
 from pvio_amd import BAState
 from oracle import oracle_py as O
 O.build()
-lib = host_compare.load("libpvio_host.so")
+if len(sys.argv) > 1:  # another build of the same harness (an A/B against another commit's adapter)
+    import ctypes
+    lib = ctypes.CDLL(sys.argv[1])
+    lib.host_roundtrip_solve.restype = lib.host_roundtrip_marginalize.restype = ctypes.c_int
+else:
+    lib = host_compare.load("libpvio_host.so")
 for nf, nl in ((10, 1000), (8, 300)):
     pb, st = marg_compare.solved_window(O, regular_prior=False, n_frames=nf, n_landmarks=nl, use_inertial=True)
     sys.stderr.write("---- %d x %d ----\n" % (nf, nl))
