@@ -327,6 +327,58 @@ int32_t pvio_hip_triangulate(pvio_hip_ctx *ctx, const pvio_tri_problem *problem,
  * and the hipEvent time of the kernel in ms -- recorded only when PVIO_HIP_TIMING is set in the environment, else 0 */
 int32_t pvio_hip_triangulate_stats(const pvio_hip_ctx *ctx, int32_t *max_sweeps, double *kernel_ms);
 
+/* Plane extraction from landmark points: a 3-point plane RANSAC and a least-squares refit of the winner's inliers.
+ * Reference: PlaneExtractor::work (core/plane_extractor.cpp:40-81) -- Ransac<3, PlaneState, PlaneSolver, PlaneEvaluator> (utility/ransac.h,
+ * core/plane_extractor.h:47-65) with threshold 0.03, confidence 0.999, 1000 iterations, seed 0 -- and the refit of plane_extractor.cpp:59-77.
+ * The result is the SEQUENTIAL algorithm's: the samples of all max_iterations hypotheses are drawn on the host, scored on the device in one
+ * launch, and the loop's bookkeeping is replayed over the counts in draw order; hypotheses past the loop's end are not looked at.
+ * Everything is FP64 without contraction (pvio_amd/csrc/pv_plane.h); a dot product is (x0 y0 + x1 y1) + x2 y2.
+ *   sample    three draws without replacement from a LotBox over 0 .. n-1 whose permutation PERSISTS over iterations (utility/random.h:108-163),
+ *             std::default_random_engine (x <- 16807 x mod (2^31 - 1); seed mod (2^31 - 1), 0 replaced by 1) and
+ *             std::uniform_int_distribution<size_t> on [cap, n - 1], both restated: the samples do not depend on the standard library.
+ *             n = 300, seed 0: the first sample is (0, 40, 227).  The third draw of n = 3 takes the last lot and no random number
+ *   model     normal = (p2 - p0) x (p1 - p0), Eigen's stableNormalize (w = max |c|, z = sum (c / w)^2, divided by sqrt(z) w only if z > 0),
+ *             distance = p0 . normal.  QUIRK KEPT: a degenerate sample (collinear or duplicate points) leaves the normal zero, the distance
+ *             is 0 and EVERY finite point is an inlier.  A sample with a non-finite coordinate has no inliers
+ *   inlier    |p . normal - distance| <= threshold; NaN is not an inlier
+ *   loop      a hypothesis replaces the best only with STRICTLY more inliers (the best starts at 0); then N = K / log(1 - (count / n)^5),
+ *             K = log(max(1 - confidence, 1e-5)), and iter_max = ceil(N) if N < iter_max.  A ratio of 1 ends the run after that iteration.
+ *             The fifth power (for a 3-point model) is the reference's: a plane that holds 20 % of the points never shortens a
+ *             1000-iteration run.  Defined where the reference converts out of range: log(..) == 0 (a ratio below 6.4e-4) changes nothing,
+ *             a negative N (confidence <= 0) counts as 0
+ *   refit     whenever n_inliers >= 3 (refit_valid = 1; else the three refit fields are 0): reference_point = cog = sum p / count,
+ *             cov = sum (p - cog)(p - cog)^T in a second pass, refit_normal = the unit eigenvector of cov's smallest eigenvalue (cyclic
+ *             Jacobi), refit_distance = refit_normal . cog.  The reference leaves the sign to Eigen; here refit_normal . normal >= 0, and
+ *             if that is exactly 0 the first non-zero component is positive.  The reference keeps a plane only if n_inliers > 30: that
+ *             rule is the caller's
+ * n_points < 3 returns PVIO_OK with the empty result: n_inliers = iterations = 0, best_iteration = -1, a zero mask, zero models (the reference
+ * returns an uninitialised model there).  So does, with `iterations` set, a run in which no hypothesis has an inlier.
+ * PVIO_ERR_INVALID_ARGUMENT, with nothing written: NULL structs; NULL points or inlier_mask with n_points > 0; n_points < 0 or > 2^24;
+ * max_iterations outside 1 .. 4096; a negative or non-finite threshold; a NaN confidence.
+ * The call owns its buffers: a window uploaded with pvio_hip_ba_upload stays uploaded and the next pvio_hip_ba_solve_resident returns the
+ * same bits as without the call.  It does not touch the communicator.  Two calls on the same input return the same bits. */
+typedef struct pvio_plane_problem {
+    int32_t n_points;              /* n >= 0 */
+    int32_t max_iterations;        /* reference: 1000; 1 .. 4096 */
+    const double *points;          /* [n][3] */
+    double threshold, confidence;  /* reference: 0.03, 0.999 */
+    uint32_t seed;                 /* reference: 0 */
+    int32_t reserved;
+} pvio_plane_problem;
+typedef struct pvio_plane_result {
+    int32_t n_inliers;        /* out */
+    int32_t iterations;       /* out: iterations the sequential loop ran (<= max_iterations) */
+    int32_t best_iteration;   /* out: index of the winning iteration, -1 when none */
+    int32_t refit_valid;      /* out: 1 when n_inliers >= 3 */
+    uint8_t *inlier_mask;     /* [n] */
+    double normal[3], distance;                   /* the RANSAC model (ransac.solve's return) */
+    double refit_normal[3], refit_distance, reference_point[3];   /* plane_extractor.cpp:59-77 */
+} pvio_plane_result;
+int32_t pvio_hip_plane_ransac(pvio_hip_ctx *ctx, const pvio_plane_problem *problem, pvio_plane_result *out);
+/* diagnostics of the last pvio_hip_plane_ransac of this context: the hypotheses the device scored, and the hipEvent times of
+ * k_plane_hypotheses and k_plane_refit in ms -- recorded only when PVIO_HIP_TIMING is set in the environment, else 0.  Either may be NULL */
+int32_t pvio_hip_plane_ransac_stats(const pvio_hip_ctx *ctx, int32_t *hypotheses_scored, double kernel_ms[2]);
+
 /* multi-GPU (landmark shards, one process per GPU): RCCL communicator bootstrap.
  * rank 0 creates the 128-byte unique id, the launcher broadcasts it (torch.distributed), every rank inits. */
 int32_t pvio_hip_comm_unique_id(uint8_t id[128]);

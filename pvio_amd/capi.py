@@ -90,6 +90,20 @@ class TriResultC(C.Structure):
 TRI_MAX_OBS = 32  # PVIO_TRI_MAX_OBS
 
 
+class PlaneProblemC(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("max_iterations", C.c_int32), ("points", c_double_p), ("threshold", C.c_double), ("confidence", C.c_double),
+                ("seed", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class PlaneResultC(C.Structure):
+    _fields_ = [("n_inliers", C.c_int32), ("iterations", C.c_int32), ("best_iteration", C.c_int32), ("refit_valid", C.c_int32), ("inlier_mask", c_uint8_p),
+                ("normal", C.c_double * 3), ("distance", C.c_double), ("refit_normal", C.c_double * 3), ("refit_distance", C.c_double),
+                ("reference_point", C.c_double * 3)]
+
+
+PLANE_MAX_ITERATIONS, PLANE_MAX_POINTS = 4096, 1 << 24  # the bounds of pvio_plane_problem
+
+
 class BAKernelTimesC(C.Structure):
     _fields_ = [("total_ms", C.c_double * 4), ("launches", C.c_int32 * 4), ("phase_ticks", (C.c_int64 * 32) * 4),
                 ("comm_ms", C.c_double * 2), ("comm_launches", C.c_int32 * 2)]
@@ -106,7 +120,7 @@ ABI_VERSION = 2  # PVIO_HIP_ABI_VERSION of include/pvio_hip.h these ctypes struc
 EXPORTS = [
     "pvio_hip_create", "pvio_hip_destroy", "pvio_hip_last_error", "pvio_hip_version", "pvio_hip_abi_version",
     "pvio_hip_ba_solve", "pvio_hip_ba_marginalize", "pvio_hip_ba_reprojection_error", "pvio_hip_ba_covariance", "pvio_hip_ba_covariance_kernel_ms",
-    "pvio_hip_triangulate", "pvio_hip_triangulate_stats",
+    "pvio_hip_triangulate", "pvio_hip_triangulate_stats", "pvio_hip_plane_ransac", "pvio_hip_plane_ransac_stats",
     "pvio_hip_ba_upload", "pvio_hip_ba_solve_resident", "pvio_hip_ba_download", "pvio_hip_ba_profile_resident", "pvio_hip_ba_last_candidate_repeats", "pvio_hip_ba_graph_replays",
     "pvio_hip_comm_unique_id", "pvio_hip_comm_init", "pvio_preintegrate",
     "pvio_hip_image_create", "pvio_hip_image_release", "pvio_hip_image_download_level", "pvio_hip_klt_track", "pvio_hip_image_detect", "pvio_hip_image_download_response",
@@ -153,6 +167,10 @@ def load(path=None):
     lib.pvio_hip_triangulate.restype = C.c_int32
     lib.pvio_hip_triangulate_stats.argtypes = [vp, c_int32_p, c_double_p]
     lib.pvio_hip_triangulate_stats.restype = C.c_int32
+    lib.pvio_hip_plane_ransac.argtypes = [vp, C.POINTER(PlaneProblemC), C.POINTER(PlaneResultC)]
+    lib.pvio_hip_plane_ransac.restype = C.c_int32
+    lib.pvio_hip_plane_ransac_stats.argtypes = [vp, c_int32_p, c_double_p]
+    lib.pvio_hip_plane_ransac_stats.restype = C.c_int32
     lib.pvio_hip_ba_reprojection_error.argtypes = [vp, C.POINTER(BAProblemC), C.POINTER(BAStateC), c_double_p]
     lib.pvio_hip_ba_reprojection_error.restype = C.c_int32
     lib.pvio_hip_ba_upload.argtypes = [vp, C.POINTER(BAProblemC), C.POINTER(BAStateC)]

@@ -7,7 +7,7 @@
 //
 // In order: upload in its five steps; the read-back layouts (SolvePack, MargGather, CovSlabs); solve in its steps (enqueue_slot, run_slots,
 // request_solve_buffers, reset_for_solve, ProfileScope, profiled_slot, time_limit_reached, fill_summary, unpack_results); the one-shot calls
-// marginalize and covariance above linearize_once; triangulate in its steps.  The marginalization's dense host algebra is marg_prior.h.
+// marginalize and covariance above linearize_once; triangulate and plane_ransac in their steps.  The marginalization's dense host algebra is marg_prior.h.
 #include "ba_solver.h"
 
 #include <algorithm>
@@ -17,8 +17,10 @@
 
 #include "ba_cov.h"
 #include "ba_kernels.h"
+#include "ba_plane.h"
 #include "ba_triangulate.h"
 #include "marg_prior.h"
+#include "pv_plane.h"
 
 namespace pvba {
 constexpr bool kDenseLookAheadDefault = true; // same-box A/B (profiles/r3_ab_lookahead.txt): 12 076 -> 12 678 iterations/s
@@ -75,6 +77,8 @@ BASolver::~BASolver() {
     for (hipEvent_t ev : cov_ev_)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : tri_ev_)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : plane_ev_)
         if (ev) (void)hipEventDestroy(ev);
     if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -1388,6 +1392,144 @@ int BASolver::triangulate(const pvio_tri_problem *pb, pvio_tri_result *out) {
     return fetch_tracks(lay, out);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// plane_ransac = validate -> stage (points + the samples of every hypothesis) -> score -> replay -> refit -> unpack (pvio_hip_plane_ransac).
+// One buffer on the device and its pinned twin on the host, both the call's own and kept between calls: neither the pool nor the View of an
+// uploaded window is touched.  Two stream round trips: the replay of the stopping rule between them runs on the host (log, pow).
+// ---------------------------------------------------------------------------------------------------------------------
+
+// a plane RANSAC call's buffer, in doubles: points | samples (int32) | counts (int32) | models | record | mask (bytes).  The upload is
+// [0, o_models) -- the counts go up as zeros --, the first read-back [o_counts, o_record), the second [o_record, n_total).
+// PVIO_HIP_PLANE_CHUNK=<points> (experiments, read at every call so that one process can time both forms; rounded up to a multiple of 64, clamped
+// to 64 .. 2^24): the points one wave of k_plane_hypotheses scores.  2^24 is the first form, a hypothesis walked by one wave.
+static int32_t plane_chunk() {
+    const char *s = std::getenv("PVIO_HIP_PLANE_CHUNK");
+    const long v = s ? std::atol(s) : (long)kPlaneChunk;
+    return (int32_t)((std::min(std::max(v, 64L), (long)kPlaneMaxPoints) + 63) / 64 * 64);
+}
+
+struct PlaneLayout {
+    size_t n = 0, H = 0, o_samples = 0, o_counts = 0, o_models = 0, o_record = 0, o_mask = 0, n_total = 0;
+    void set(size_t n_, size_t H_) {
+        n = n_, H = H_;
+        o_samples = 3 * n, o_counts = o_samples + (3 * H + 1) / 2, o_models = o_counts + (H + 1) / 2, o_record = o_models + 4 * H;
+        o_mask = o_record + kPlaneRecord, n_total = o_mask + (n + 7) / 8;
+    }
+    PlaneArgs args(double *d, double threshold) const {
+        PlaneArgs a{};
+        a.n = (int32_t)n, a.n_hyp = (int32_t)H, a.chunk = plane_chunk(), a.threshold = threshold;
+        a.points = d, a.samples = reinterpret_cast<const int32_t *>(d + o_samples), a.counts = reinterpret_cast<int32_t *>(d + o_counts);
+        a.models = d + o_models, a.record = d + o_record, a.mask = reinterpret_cast<uint8_t *>(d + o_mask);
+        return a;
+    }
+};
+
+// every rejection of include/pvio_hip.h, before anything is written anywhere
+int BASolver::validate_points(const pvio_plane_problem *pb, const pvio_plane_result *out) {
+    if (!pb || !out) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_plane_ransac: null argument");
+    if (pb->n_points < 0 || pb->n_points > kPlaneMaxPoints) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_plane_ransac: n_points outside [0, 2^24]");
+    if (pb->n_points > 0 && (!pb->points || !out->inlier_mask)) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_plane_ransac: null points or inlier_mask");
+    if (pb->max_iterations < 1 || pb->max_iterations > kPlaneMaxIterations) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_plane_ransac: max_iterations outside [1, 4096]");
+    if (!std::isfinite(pb->threshold) || pb->threshold < 0.0) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_plane_ransac: the threshold is negative or not finite");
+    if (std::isnan(pb->confidence)) return fail(PVIO_ERR_INVALID_ARGUMENT, "pvio_hip_plane_ransac: the confidence is NaN");
+    return PVIO_OK;
+}
+
+// the points and the samples of all H hypotheses, in the order the sequential loop would draw them, into the pinned twin; then ONE copy up
+int BASolver::stage_points(const pvio_plane_problem *pb, const PlaneLayout &lay) {
+    const size_t bytes = lay.n_total * sizeof(double);
+    if (!d_plane_.reserve(bytes, bytes + bytes / 2)) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipMalloc failed (plane RANSAC buffer)");
+    double *const h = static_cast<double *>(h_plane_.reserve(bytes, bytes + bytes / 2));
+    if (!h) return fail(PVIO_ERR_OUT_OF_MEMORY, "hipHostMalloc failed (plane RANSAC buffer)");
+    std::memcpy(h, pb->points, 3 * lay.n * sizeof(double));
+    h[lay.o_counts - 1] = 0.0; // the int array's padding
+    std::memset(h + lay.o_counts, 0, (lay.o_models - lay.o_counts) * sizeof(double)); // the counts start at 0
+    int32_t *const samples = reinterpret_cast<int32_t *>(h + lay.o_samples);
+    pvpl::PlSampler sampler((int)lay.n, pb->seed);
+    for (size_t k = 0; k < lay.H; ++k) sampler.sample(samples + 3 * k);
+    return check(hipMemcpyAsync(d_plane_.data(), h, lay.o_models * sizeof(double), hipMemcpyHostToDevice, stream_), "plane_ransac H2D");
+}
+
+// k_plane_hypotheses over every hypothesis; counts and models come back
+int BASolver::score_hypotheses(const PlaneLayout &lay, double threshold) {
+    const bool timing = solver_switches().timing; // diagnostics: hipEvents around the kernels
+    if (timing)
+        for (hipEvent_t &ev : plane_ev_)
+            if (!ev && check(hipEventCreate(&ev), "hipEventCreate")) return PVIO_ERR_HIP;
+    if (timing) (void)hipEventRecord(plane_ev_[0], stream_);
+    const hipError_t e = launch_plane_hypotheses(lay.args(d_plane_.as<double>(), threshold), stream_);
+    if (e != hipSuccess) return check(e, "k_plane_hypotheses");
+    if (timing) (void)hipEventRecord(plane_ev_[1], stream_);
+    double *const h = h_plane_.as<double>();
+    if (check(hipMemcpyAsync(h + lay.o_counts, d_plane_.as<double>() + lay.o_counts, (lay.o_record - lay.o_counts) * sizeof(double), hipMemcpyDeviceToHost, stream_), "plane_ransac D2H (counts)")) return PVIO_ERR_HIP;
+    if (check(hipStreamSynchronize(stream_), "plane_ransac sync")) return PVIO_ERR_HIP;
+    stage_in_flight_ = false; // whatever an upload left queued on the stream has been read as well
+    plane_scored_ = (int)lay.H;
+    if (timing) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, plane_ev_[0], plane_ev_[1]);
+        plane_ms_[0] = ms;
+    }
+    return PVIO_OK;
+}
+
+// k_plane_refit for the winning model; record and mask come back
+int BASolver::refit_winner(const PlaneLayout &lay, double threshold, const double *model) {
+    const bool timing = solver_switches().timing;
+    PlaneArgs a = lay.args(d_plane_.as<double>(), threshold);
+    for (int k = 0; k < 4; ++k) a.model[k] = model[k];
+    if (timing) (void)hipEventRecord(plane_ev_[2], stream_);
+    const hipError_t e = launch_plane_refit(a, stream_);
+    if (e != hipSuccess) return check(e, "k_plane_refit");
+    if (timing) (void)hipEventRecord(plane_ev_[3], stream_);
+    double *const h = h_plane_.as<double>();
+    if (check(hipMemcpyAsync(h + lay.o_record, d_plane_.as<double>() + lay.o_record, (lay.n_total - lay.o_record) * sizeof(double), hipMemcpyDeviceToHost, stream_), "plane_ransac D2H (refit)")) return PVIO_ERR_HIP;
+    if (check(hipStreamSynchronize(stream_), "plane_ransac sync")) return PVIO_ERR_HIP;
+    if (timing) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, plane_ev_[2], plane_ev_[3]);
+        plane_ms_[1] = ms;
+    }
+    return PVIO_OK;
+}
+
+int BASolver::plane_ransac(const pvio_plane_problem *pb, pvio_plane_result *out) {
+    int rc = validate_points(pb, out);
+    if (rc != PVIO_OK) return rc;
+    plane_scored_ = 0, plane_ms_[0] = plane_ms_[1] = 0.0;
+    const size_t n = (size_t)pb->n_points;
+    uint8_t *const mask = out->inlier_mask; // (the empty result: zeros everywhere, no winner)
+    *out = pvio_plane_result{};
+    out->inlier_mask = mask, out->best_iteration = -1;
+    if (n > 0) std::memset(mask, 0, n);
+    if (n < 3) return PVIO_OK; // ransac.h:53-57
+    PlaneLayout lay;
+    lay.set(n, (size_t)pb->max_iterations);
+    if ((rc = stage_points(pb, lay)) != PVIO_OK) return rc;
+    if ((rc = score_hypotheses(lay, pb->threshold)) != PVIO_OK) return rc;
+    // the sequential loop's bookkeeping over the counts, in the order the samples were drawn; hypotheses beyond its end are not looked at
+    const double *const h = h_plane_.as<double>();
+    const int32_t *const counts = reinterpret_cast<const int32_t *>(h + lay.o_counts);
+    pvpl::PlBest run(pb->confidence, pb->max_iterations);
+    int iter = 0;
+    for (; iter < run.iter_max; ++iter) run.offer(counts[iter], iter, (int)n);
+    out->iterations = iter;
+    if (run.best_iter < 0) return PVIO_OK; // no hypothesis had an inlier (a zero threshold, non-finite points)
+    const double *const model = h + lay.o_models + 4 * (size_t)run.best_iter;
+    if ((rc = refit_winner(lay, pb->threshold, model)) != PVIO_OK) return rc;
+    const double *const rec = h + lay.o_record;
+    if ((int)rec[0] != run.count)
+        return fail(PVIO_ERR_HIP, "pvio_hip_plane_ransac: k_plane_refit counts " + std::to_string((int)rec[0]) + " inliers of the winning model, k_plane_hypotheses counted " + std::to_string(run.count));
+    out->n_inliers = run.count, out->best_iteration = run.best_iter, out->refit_valid = rec[1] != 0.0 ? 1 : 0;
+    std::memcpy(mask, h + lay.o_mask, n);
+    std::memcpy(out->normal, model, 3 * sizeof(double));
+    out->distance = model[3];
+    std::memcpy(out->refit_normal, rec + 2, 3 * sizeof(double));
+    out->refit_distance = rec[5];
+    std::memcpy(out->reference_point, rec + 6, 3 * sizeof(double));
+    return PVIO_OK;
+}
+
 } // namespace pvba
 
 // The kernels of covariance() and their launchers.  They are compiled as part of this translation unit, not as an object of their own: whatever
@@ -1396,3 +1538,5 @@ int BASolver::triangulate(const pvio_tri_problem *pb, pvio_tri_result *out) {
 #include "ba_cov.hip"
 // The kernel of triangulate() and its launcher, for the same reason.
 #include "ba_triangulate.hip"
+// ... and the kernels of plane_ransac().
+#include "ba_plane.hip"

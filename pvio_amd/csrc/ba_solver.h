@@ -40,6 +40,7 @@ struct UploadWork; // the View an upload is building
 struct SolvePack;  // layout of a solve's packed read-back
 struct MargGather; // layout of a marginalization's gathered read-back
 struct TriLayout;  // layout of a triangulation call's device buffer
+struct PlaneLayout; // layout of a plane RANSAC call's device buffer
 
 class BASolver {
   public:
@@ -63,6 +64,9 @@ class BASolver {
     int triangulate(const pvio_tri_problem *pb, pvio_tri_result *out); // batched DLT triangulation (ba_triangulate.hip); leaves an uploaded window alone
     int last_triangulate_sweeps() const { return tri_sweeps_; }        // most Jacobi sweeps a track of the last call took
     double last_triangulate_kernel_ms() const { return tri_ms_; }      // k_triangulate of the last call (PVIO_HIP_TIMING)
+    int plane_ransac(const pvio_plane_problem *pb, pvio_plane_result *out); // plane RANSAC + refit over points (ba_plane.hip); leaves an uploaded window alone
+    int last_plane_hypotheses() const { return plane_scored_; }             // hypotheses k_plane_hypotheses scored in the last call
+    const double *last_plane_kernel_ms() const { return plane_ms_; }        // k_plane_hypotheses, k_plane_refit of the last call (PVIO_HIP_TIMING)
     void set_comm(Comm *c) { comm_ = c; }
     const std::string &error() const { return err_; }
     hipStream_t stream() const { return stream_; }
@@ -90,6 +94,11 @@ class BASolver {
     int stage_tracks(const pvio_tri_problem *pb, const TriLayout &lay);
     int launch_tracks(const TriLayout &lay);
     int fetch_tracks(const TriLayout &lay, pvio_tri_result *out);
+    // the steps of plane_ransac() (ba_solver.cpp)
+    int validate_points(const pvio_plane_problem *pb, const pvio_plane_result *out);
+    int stage_points(const pvio_plane_problem *pb, const PlaneLayout &lay);
+    int score_hypotheses(const PlaneLayout &lay, double threshold);
+    int refit_winner(const PlaneLayout &lay, double threshold, const double *model);
     // the steps of upload() behind its argument checks (ba_solver.cpp)
     void plan_upload(const pvio_ba_problem *pb, UploadPlan &plan) const;
     int allocate(UploadWork &w);
@@ -125,6 +134,11 @@ class BASolver {
     hipEvent_t tri_ev_[2] = {nullptr, nullptr}; // around k_triangulate, created on first use (PVIO_HIP_TIMING)
     int tri_sweeps_ = 0;
     double tri_ms_ = 0.0;
+    pvhip::DeviceBuffer d_plane_; // a plane RANSAC call's points, samples, counts, models, record and mask (its own: the window's buffers are not touched)
+    pvhip::PinnedBuffer h_plane_; // pinned staging and read-back of the same layout
+    hipEvent_t plane_ev_[4] = {nullptr, nullptr, nullptr, nullptr}; // around the two kernels, created on first use (PVIO_HIP_TIMING)
+    int plane_scored_ = 0;
+    double plane_ms_[2] = {0.0, 0.0};
     pvhip::PinnedBuffer h_pack_; // pinned: a solve's packed results (k_quality `pack`, doubles)
     const double *fs_init_ = nullptr, *rho_init_ = nullptr; // initial state inside the inputs slab
     Ctrl h_ctrl_tmpl_{};                                    // what a solve's control block starts from (k_reset copies the device copy)

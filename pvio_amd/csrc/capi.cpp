@@ -119,6 +119,17 @@ int32_t pvio_hip_triangulate_stats(const pvio_hip_ctx *ctx, int32_t *max_sweeps,
     if (kernel_ms) *kernel_ms = ctx->ba->last_triangulate_kernel_ms();
     return PVIO_OK;
 }
+int32_t pvio_hip_plane_ransac(pvio_hip_ctx *ctx, const pvio_plane_problem *problem, pvio_plane_result *out) {
+    if (!ctx || !ctx->ba) return PVIO_ERR_INVALID_ARGUMENT;
+    return ctx->ba->plane_ransac(problem, out); // (its argument checks leave a message for pvio_hip_last_error)
+}
+int32_t pvio_hip_plane_ransac_stats(const pvio_hip_ctx *ctx, int32_t *hypotheses_scored, double kernel_ms[2]) {
+    if (!ctx || !ctx->ba) return PVIO_ERR_INVALID_ARGUMENT;
+    if (hypotheses_scored) *hypotheses_scored = ctx->ba->last_plane_hypotheses();
+    if (kernel_ms)
+        for (int k = 0; k < 2; ++k) kernel_ms[k] = ctx->ba->last_plane_kernel_ms()[k];
+    return PVIO_OK;
+}
 int32_t pvio_hip_ba_reprojection_error(pvio_hip_ctx *ctx, const pvio_ba_problem *problem, const pvio_ba_state *state, double *mean_pixel_error) {
     if (!ctx || !problem || !state || !mean_pixel_error) return PVIO_ERR_INVALID_ARGUMENT;
     int rc = ctx->ba->upload(problem, state);

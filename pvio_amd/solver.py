@@ -168,6 +168,30 @@ class HipContext:
         self._check(self.lib.pvio_hip_triangulate_stats(self.ctx, C.byref(sweeps), C.byref(ms)), "pvio_hip_triangulate_stats")
         return int(sweeps.value), float(ms.value)
 
+    def plane_ransac(self, points, threshold=0.03, confidence=0.999, max_iterations=1000, seed=0):
+        """pvio_hip_plane_ransac: the reference's 3-point plane RANSAC over points [n, 3] and the least-squares refit of the winner's inliers
+        (include/pvio_hip.h; the defaults are PlaneExtractor::work's).  Returns a dict: n_inliers, iterations, best_iteration, refit_valid,
+        inlier_mask [n] (uint8), normal [3], distance, refit_normal [3], refit_distance, reference_point [3].  The reference keeps the plane
+        only if n_inliers > 30: that rule is the caller's."""
+        points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        n = points.shape[0]
+        mask = np.zeros(n, np.uint8)
+        pb, out = capi.PlaneProblemC(), capi.PlaneResultC()
+        pb.n_points, pb.max_iterations, pb.points = n, max_iterations, points.ctypes.data_as(capi.c_double_p)
+        pb.threshold, pb.confidence, pb.seed = threshold, confidence, seed
+        out.inlier_mask = mask.ctypes.data_as(capi.c_uint8_p)
+        self._check(self.lib.pvio_hip_plane_ransac(self.ctx, C.byref(pb), C.byref(out)), "pvio_hip_plane_ransac")
+        return dict(n_inliers=int(out.n_inliers), iterations=int(out.iterations), best_iteration=int(out.best_iteration), refit_valid=int(out.refit_valid),
+                    inlier_mask=mask, normal=np.array(out.normal[:]), distance=float(out.distance), refit_normal=np.array(out.refit_normal[:]),
+                    refit_distance=float(out.refit_distance), reference_point=np.array(out.reference_point[:]))
+
+    def plane_ransac_stats(self):
+        """(hypotheses_scored, kernel_ms [2]) of the last plane_ransac(): the hypotheses the device scored; the hipEvent times of
+        k_plane_hypotheses and k_plane_refit, recorded only with PVIO_HIP_TIMING set (else 0)"""
+        scored, ms = C.c_int32(0), np.zeros(2)
+        self._check(self.lib.pvio_hip_plane_ransac_stats(self.ctx, C.byref(scored), ms.ctypes.data_as(capi.c_double_p)), "pvio_hip_plane_ransac_stats")
+        return int(scored.value), ms
+
     def triangulate_window(self, problem, state, planes=False):
         """The landmarks of a flattened window (or, planes=True, its plane tracks) triangulated from the camera poses of `state`.  Views are
         the frames' cameras (Frame::get_pose(camera): q_c = q_b * q_cs, p_c = p_b + R(q_b) p_cs); a landmark's track is its anchor observation
